@@ -2,7 +2,9 @@
 """Headline benchmark: decode tokens/s + p50 TTFT, Llama-3.1-8B FP8 weights, block_size=32,
 max_num_seqs=4 (BASELINE.json), on N MI355X GPUs of one node.
 
-    python bench.py --gpus 1 --steps 64 --warmup 8
+    python bench.py --gpus 1 --steps 64 --warmup 8     (the headline figure and nothing else)
+    python bench.py --gpus 1 ... --full                (+ every other section of the line, see below)
+    python bench.py --gpus 1 ... --dump-outputs DIR    (+ DIR/logits.npy: what the last step computed)
     python bench.py --gpus N ...                       (one process drives the N GPUs, see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -13,7 +15,18 @@ libmi355x_vllm.  The timed region is exactly K steps with every input resident i
 (mi_replay_decode: hipGraph replays bracketed by HIP events on the library's stream, and by
 barrier + torch.cuda.synchronize on both sides); `value` = B * K / max-over-ranks time.
 
-What the line says, key by key:
+A plain run builds the engine, encodes the B contexts, captures the step, replays W warm-up steps, times the K steps, writes
+--dump-outputs and prints the line: value / ms_per_step and the description of the workload.  Every other
+key below takes runs of its own (more engines, prompt sweeps, the CPU oracle) and is measured only
+with --full, after the headline, so that the headline is the same measurement in both modes.
+
+--dump-outputs DIR writes DIR/logits.npy, float32 [B, vocab]: the logits of the timed step.  The
+replays leave them on the device, so they are fetched by one more launch of the same captured graph
+on the same resident inputs through mi_forward.  Weights, token ids and block tables are seeded, and
+the KV pool starts zeroed and is filled by encoding the B seeded 1023-token contexts before the step:
+the same arguments give the same inputs in every run and every build.
+
+What the line says, key by key (everything after ms_per_step: --full only):
   value / ms_per_step          the DEVICE step: the hot path replayed with resident inputs -- no
                                scheduler, no H2D, no logits D2H, no sampler.  Kernel quality.
   engine_decode_tokens_per_s   what a user of the plugin sees: scheduler -> runner -> library ->
@@ -275,15 +288,22 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--model", default="llama31_8b", choices=["llama31_8b", "qwen25_7b", "llama33_70b"])
-    ap.add_argument("--ttft-prompts", type=int, default=32, help="prompts per context-encoding bucket (p50)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-speculation", action="store_true", help="skip the fused-speculation timing section")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure every other section of the line (TTFT sweeps, engine-loop rates, "
+                         "other contexts, roofline, speculation, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the timed step to DIR/logits.npy (float32 [max_num_seqs, vocab])")
+    ap.add_argument("--ttft-prompts", type=int, default=32, help="--full: prompts per context-encoding bucket (p50)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline")
+    ap.add_argument("--no-speculation", action="store_true", help="--full: skip the fused-speculation timing section")
     ap.add_argument("--weight-dtype", default=None, choices=["f8e4m3", "int8", "bf16"],
                     help="default: f8e4m3 (int8 for qwen25_7b)")
     ap.add_argument("--tp-transport", default="p2p", choices=["p2p", "rccl"])
     ap.add_argument("--tp-loopback", action="store_true",
                     help="dev: place every rank shard of --gpus N on GPU 0 (functional check of the TP path on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     wd = args.weight_dtype or ("int8" if args.model == "qwen25_7b" else "f8e4m3")
     HF = MODELS[args.model]
 
@@ -368,6 +388,73 @@ def main():
     native = eng.worker.model_runner.model.model
     init_s = time.perf_counter() - t0
 
+    # ---- decode: B sequences at context DECODE_CTX: the timed region (first, and the same in a plain and a --full run) ----
+    from tests.helpers import decode_inputs, prefill_inputs
+    mb = MAX_MODEL_LEN // BLOCK_SIZE
+    perm = (torch.randperm(PA_NUM_BLOCKS, generator=torch.Generator().manual_seed(2)) + 1).tolist()
+    blocks = [perm[b * mb:(b + 1) * mb] for b in range(MAX_NUM_SEQS)]
+    # the context of the step: every sequence's first DECODE_CTX - 1 tokens (seeded) encoded into its blocks, so that the step
+    # attends over real keys and values and the dumped logits depend on every kernel of the path and on every block it reads
+    g4 = torch.Generator().manual_seed(4)
+    for b in range(MAX_NUM_SEQS):
+        prompt = torch.randint(0, hf.vocab_size, (DECODE_CTX - 1,), generator=g4).tolist()
+        native.forward(**prefill_inputs(prompt, blocks[b], BLOCK_SIZE, MAX_MODEL_LEN, 0))
+    toks = torch.randint(0, hf.vocab_size, (MAX_NUM_SEQS,), generator=g4).tolist()
+    inp = decode_inputs(toks, [DECODE_CTX - 1] * MAX_NUM_SEQS, blocks, BLOCK_SIZE, MAX_MODEL_LEN)
+    for _ in range(2):
+        native.forward(**inp)                            # captures the graph, leaves inputs resident
+    native.replay_decode(max(args.warmup, 1))            # W untimed warm-up steps
+    barrier_sync()
+    t = time.perf_counter()
+    dev_ms = native.replay_decode(args.steps)            # exactly K timed steps
+    for d in range(1 if args.tp_loopback else tp):
+        torch.cuda.synchronize(d)
+    wall = time.perf_counter() - t
+    barrier_sync()
+    if world > 1:
+        tt = torch.tensor([wall], dtype=torch.float64)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        wall = float(tt[0])
+    ms_per_step = wall * 1e3 / args.steps
+    value = MAX_NUM_SEQS * args.steps / wall
+
+    if args.dump_outputs:
+        # the replays keep their logits on the device: the same graph once more on the same resident inputs, logits D2H
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), native.forward(**inp).to(torch.float32).numpy())
+
+    label = MODEL_LABEL[args.model]
+    wname = {"f8e4m3": "FP8", "int8": "INT8", "bf16": "bf16"}[wd]
+    line = {
+        "metric": f"decode tokens/sec ({label} {wname}, block_size=32, max_num_seqs=4): device step with resident inputs; "
+                  "p50 TTFT in ttft_p50_ms; engine-level rate in engine_decode_tokens_per_s",
+        "value": round(value, 2), "unit": "tokens/s", "n_gpus": tp, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None,
+        "dtype": {"f8e4m3": "fp8_e4m3 weights x bf16 activations (weight-only quantization), f32 accumulate",
+                  "int8": "int8 weights x bf16 activations, f32 accumulate",
+                  "bf16": "bf16, f32 accumulate"}[wd],
+        "data": "synthetic (seeded N(0,0.02) weights at real shapes; random token ids)",
+        "config": {"workload": f"{label} {wd} TP={tp}: token generation B={MAX_NUM_SEQS} "
+                               f"ctx={DECODE_CTX}, block_size={BLOCK_SIZE}, pa_num_blocks={PA_NUM_BLOCKS}, "
+                               f"max_model_len={MAX_MODEL_LEN}, buckets={BUCKETS}",
+                   "parallelism": f"tp{tp}" + (" (all shards on GPU 0: functional check)" if args.tp_loopback else ""),
+                   "global_batch": MAX_NUM_SEQS, "ctx": DECODE_CTX},
+        "device_ms_per_step": round(dev_ms / args.steps, 4), "init_s": round(init_s, 2), "full": args.full,
+    }
+    if tp > 1:
+        # what the tensor-parallel group actually ran on (VERDICT r2 4d): "N ranks over peer memory, in hipGraphs" and
+        # "fell back to RCCL, eager" must be told apart in a SCALE record
+        try:
+            line["tp"] = native.tp_info()
+        except Exception as ex:                                   # noqa: BLE001 -- the bench line must still be printed
+            line["tp"] = {"error": str(ex)}
+        if tp_note:
+            line["tp"]["note"] = tp_note
+    if not args.full:
+        return finish(line)
+
     # ---- p50 TTFT per bucket, through scheduler -> runner -> library -> CPU sampler ----------
     def ttft_sweep(engine, tag):
         g = torch.Generator().manual_seed(0)            # the same prompts for every mode
@@ -399,9 +486,9 @@ def main():
             same, qual, qual_same, rms_all, gap_all = 0, 0, 0, [], []
             for _ in range(args.ttft_prompts):
                 prompt = torch.randint(0, hf.vocab_size, (bucket - 17,), generator=ga).tolist()
-                inp = prefill_inputs(prompt, blocks_a, BLOCK_SIZE, MAX_MODEL_LEN, 0)
-                lw = native.forward(**inp)[0].double()
-                la = native2.forward(**inp)[0].double()
+                pre = prefill_inputs(prompt, blocks_a, BLOCK_SIZE, MAX_MODEL_LEN, 0)
+                lw = native.forward(**pre)[0].double()
+                la = native2.forward(**pre)[0].double()
                 top2 = torch.topk(lw, 2).values
                 gap = float(top2[0] - top2[1])
                 rms = float((la - lw).pow(2).mean().sqrt())
@@ -482,11 +569,6 @@ def main():
         del engc
 
     # ---- decode at other context lengths (ctx 256 / 1024 / 2040), device-resident ---
-    from tests.helpers import decode_inputs
-    mb = MAX_MODEL_LEN // BLOCK_SIZE
-    perm = (torch.randperm(PA_NUM_BLOCKS, generator=torch.Generator().manual_seed(2)) + 1).tolist()
-    blocks = [perm[b * mb:(b + 1) * mb] for b in range(MAX_NUM_SEQS)]
-    toks = torch.randint(0, hf.vocab_size, (MAX_NUM_SEQS,), generator=g).tolist()
     by_ctx = {}
     for ctx_len in (256, 2040):
         inp_c = decode_inputs(toks, [ctx_len - 1] * MAX_NUM_SEQS, blocks, BLOCK_SIZE, MAX_MODEL_LEN)
@@ -495,25 +577,6 @@ def main():
         native.replay_decode(8)
         n_c = max(args.steps // 2, 8)
         by_ctx[str(ctx_len)] = round(MAX_NUM_SEQS * n_c / (native.replay_decode(n_c) * 1e-3), 1)
-
-    # ---- decode: B sequences at context DECODE_CTX: the timed region ----------------------------
-    inp = decode_inputs(toks, [DECODE_CTX - 1] * MAX_NUM_SEQS, blocks, BLOCK_SIZE, MAX_MODEL_LEN)
-    for _ in range(2):
-        native.forward(**inp)                            # captures the graph, leaves inputs resident
-    native.replay_decode(max(args.warmup, 1))            # W untimed warm-up steps
-    barrier_sync()
-    t = time.perf_counter()
-    dev_ms = native.replay_decode(args.steps)            # exactly K timed steps
-    for d in range(1 if args.tp_loopback else tp):
-        torch.cuda.synchronize(d)
-    wall = time.perf_counter() - t
-    barrier_sync()
-    if world > 1:
-        tt = torch.tensor([wall], dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        wall = float(tt[0])
-    ms_per_step = wall * 1e3 / args.steps
-    value = MAX_NUM_SEQS * args.steps / wall
 
     # PCIe-inclusive rate: the same step through mi_forward (ids H2D, [B, V] fp32 logits D2H)
     t = time.perf_counter()
@@ -586,23 +649,7 @@ def main():
                  "note": "whole TTFT (scheduler, H2D, every kernel of the bucket, logits D2H, CPU sampler) against the dense MFMA "
                          "peak of the dtype; prompts are bucket - 17 tokens; flops = 2 (W - lm_head) N + 2 lm_head + 4 L nh hd N^2 / 2 (SURVEY 8d counts the lm_head for every token: 7 % more)"}
 
-    label = MODEL_LABEL[args.model]
-    wname = {"f8e4m3": "FP8", "int8": "INT8", "bf16": "bf16"}[wd]
-    line = {
-        "metric": f"decode tokens/sec ({label} {wname}, block_size=32, max_num_seqs=4): device step with resident inputs; "
-                  "p50 TTFT in ttft_p50_ms; engine-level rate in engine_decode_tokens_per_s",
-        "value": round(value, 2), "unit": "tokens/s", "n_gpus": tp, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None,
-        "dtype": {"f8e4m3": "fp8_e4m3 weights x bf16 activations (weight-only quantization), f32 accumulate",
-                  "int8": "int8 weights x bf16 activations, f32 accumulate",
-                  "bf16": "bf16, f32 accumulate"}[wd],
-        "data": "synthetic (seeded N(0,0.02) weights at real shapes; random token ids)",
-        "config": {"workload": f"{label} {wd} TP={tp}: token generation B={MAX_NUM_SEQS} "
-                               f"ctx={DECODE_CTX}, block_size={BLOCK_SIZE}, pa_num_blocks={PA_NUM_BLOCKS}, "
-                               f"max_model_len={MAX_MODEL_LEN}, buckets={BUCKETS}",
-                   "parallelism": f"tp{tp}" + (" (all shards on GPU 0: functional check)" if args.tp_loopback else ""),
-                   "global_batch": MAX_NUM_SEQS, "ctx": DECODE_CTX},
+    line.update({
         "engine_decode_tokens_per_s": engine_cpu,
         "engine_decode_tokens_per_s_on_device_sampling": engine_dev,
         "engine_decode_tokens_per_s_on_device_sampling_top_k50_top_p09": engine_dev_sampled,
@@ -614,21 +661,11 @@ def main():
                                            if agreement_gated else None),
         "ttft_frac_of_mfma_peak": ttft_frac,
         "prefix_cache_ttft_ms": prefix_ttft,
-        "device_ms_per_step": round(dev_ms / args.steps, 4),
         "decode_tokens_per_s_by_ctx": {**by_ctx, str(DECODE_CTX): round(value, 1)},
         "pcie_inclusive_tokens_per_s": round(MAX_NUM_SEQS / e2e, 2),
         "speculation": speculation,
-        "init_s": round(init_s, 2), "roofline": roofline, "cpu_baseline": cpu,
-    }
-    if tp > 1:
-        # what the tensor-parallel group actually ran on (VERDICT r2 4d): "N ranks over peer memory, in hipGraphs" and
-        # "fell back to RCCL, eager" must be told apart in a SCALE record
-        try:
-            line["tp"] = native.tp_info()
-        except Exception as ex:                                   # noqa: BLE001 -- the bench line must still be printed
-            line["tp"] = {"error": str(ex)}
-        if tp_note:
-            line["tp"]["note"] = tp_note
+        "roofline": roofline, "cpu_baseline": cpu,
+    })
     finish(line)
 
 

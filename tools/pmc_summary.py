@@ -1,8 +1,8 @@
 """Dev tool: HBM traffic of the decode GEMVs from a rocprofv3 --pmc FETCH_SIZE pass of bench.py.
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc -o bench -- \
-        python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --ttft-prompts 1
-    python tools/pmc_summary.py gpurun_out/pmc profiles/r01_gemv_traffic.json
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d profiles_out/pmc -o bench -- \
+        python3 bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --ttft-prompts 1
+    python tools/pmc_summary.py profiles_out/pmc profiles/r01_gemv_traffic.json
 
 Correction per /opt/skills/guides/MI355X_MICROARCH.md (HBM): FETCH_SIZE is in KiB and on gfx950
 reports exactly half of the bytes of a wide coalesced streaming read -> bytes = value * 1024 * 2.
@@ -27,7 +27,7 @@ doc = {
     "kernel_source_sha1": hashlib.sha1(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                          "vllm-neuron_amd", "csrc", "linear_kernels.hip"), "rb").read()).hexdigest(),
     "counter": "FETCH_SIZE (KiB) x 1024 x 2: gfx950 tallies 128-B requests at 64 B (MI355X_MICROARCH.md, HBM)",
-    "command": "rocprofv3 --pmc FETCH_SIZE --output-format csv -- python3 bench.py --steps 4 --warmup 1 "
+    "command": "rocprofv3 --pmc FETCH_SIZE --output-format csv -- python3 bench.py --steps 4 --warmup 1 --full "
                "--no-cpu-baseline --ttft-prompts 1",
 }
 json.dump(doc, open(out, "w"), indent=1)
