@@ -89,12 +89,19 @@ typedef struct mi_model_config {
    * shards: the library's own all-reduce over peer-mapped memory (xGMI), or RCCL. */
   int32_t tp_device_ids[16];
   int32_t tp_transport; /* MI_TP_TRANSPORT_* */
+  /* Element type of the paged KV pool (vLLM's kv_cache_dtype): MI_KV_BF16 (0, the default) or MI_KV_F8E4M3: OCP e4m3fn
+   * codes with static per-layer fp32 scales, loaded by mi_load_weight under "model.layers.<l>.self_attn.k_scale" /
+   * ".v_scale" (scalar; default 1.0; legal until the first forward, mi_finalize included; a bf16-KV context accepts and
+   * ignores them).  write: code = rne_e4m3(clamp(float(x_bf16) * (1.0f / scale), -448, 448)); read: float(code) * scale.
+   * The scales are not part of the .miw images: a caller that restarts from mi_load_weights_file sends them again. */
+  int32_t kv_cache_dtype;
 } mi_model_config;
+enum { MI_KV_BF16 = 0, MI_KV_F8E4M3 = 1 };
 #define MI_TP_ALL_RANKS (-1)
 enum { MI_TP_TRANSPORT_P2P = 0, MI_TP_TRANSPORT_RCCL = 1 };
 
 const char* mi_last_error(void);
-int mi_version(void);   /* 4 = this header (+ mi_tp_plan, mi_tp_info); 3 lacked them; 2 lacked tp_device_ids / tp_transport / MI_TP_ALL_RANKS; 1 lacked mi_forward_tokens, mi_op_sample, mi_tp_init_transport */
+int mi_version(void);   /* 5 = this header (+ kv_cache_dtype and the FP8-KV entry points mi_op_kv_write_f8, mi_op_paged_attn_decode_f8, mi_op_kv_dequant_gather); 4 lacked them (+ mi_tp_plan, mi_tp_info); 3 lacked those; 2 lacked tp_device_ids / tp_transport / MI_TP_ALL_RANKS; 1 lacked mi_forward_tokens, mi_op_sample, mi_tp_init_transport */
 
 int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out);
 int mi_ctx_destroy(mi_ctx* ctx);
@@ -337,6 +344,34 @@ int mi_op_paged_attn_prefill(const void* q, int32_t T, int32_t q_pos0, const voi
                              int32_t num_blocks, int32_t block_size, const int32_t* block_table,
                              int32_t MB, int32_t nh, int32_t nkv, int32_t hd, void* out,
                              void* stream);
+
+/* ---- FP8 (OCP e4m3fn) paged KV, per-kernel entry points (ABI 5) --------------------------------
+ * pool_u8 layout: [2][num_blocks][nkv][block_size][hd] BYTES (K codes, then V codes), zero-filled
+ * by its owner (byte 0 is 0.0).  k_scale / v_scale: static fp32 scales (vLLM's k_scale / v_scale).
+ *   write: code  = rne_e4m3(clamp(float(x_bf16) * (1.0f / scale), -448, 448))   (saturates: no NaN code)
+ *   read:  value = float(code) * scale                                          (e4m3 -> bf16 is exact)
+ * These are the kernels a context with kv_cache_dtype = MI_KV_F8E4M3 runs. */
+/* mi_op_kv_write with the write rule above: one 4-byte store per 4 values. */
+int mi_op_kv_write_f8(const void* k, const void* v, const int64_t* slots, int32_t T, int32_t nkv,
+                      int32_t hd, void* pool_u8, int32_t num_blocks, int32_t block_size,
+                      float k_scale, float v_scale, void* stream);
+/* mi_op_paged_attn_decode over the byte pool (same arguments, same scratch size).  K codes go from
+ * the pool straight into registers, V codes through a wave-private LDS tile read back transposed
+ * by ds_read_b64_tr_b8; both are widened to bf16 in registers and every MFMA is the bf16 one.
+ * k_scale is folded into the score scale, v_scale applied once to the merged output. */
+int mi_op_paged_attn_decode_f8(const void* q, const void* pool_u8, int32_t num_blocks,
+                               int32_t block_size, const int32_t* block_table, int32_t MB,
+                               const int32_t* ctx_lens, int32_t B, int32_t nh, int32_t nkv,
+                               int32_t hd, float k_scale, float v_scale, void* out, void* scratch,
+                               void* stream);
+/* Context encoding over an FP8 pool: stage ONE sequence's keys 0 .. kv_len - 1 as bf16.
+ * block_table [MB] int32; staged_bf16 [2][ceil(kv_len / block_size)][nkv][block_size][hd] bf16 in
+ * block-table order, element bf16_rne(float(code) * scale).  mi_op_paged_attn_prefill then runs on
+ * staged_bf16 with num_blocks = ceil(kv_len / block_size) and the identity block table. */
+int mi_op_kv_dequant_gather(const void* pool_u8, int32_t num_blocks, int32_t block_size,
+                            const int32_t* block_table, int32_t MB, int32_t kv_len, int32_t nkv,
+                            int32_t hd, float k_scale, float v_scale, void* staged_bf16,
+                            void* stream);
 
 #ifdef __cplusplus
 }

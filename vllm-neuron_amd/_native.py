@@ -10,6 +10,7 @@ the process holds ONE HIP runtime (torch device pointers are then valid here).
 from __future__ import annotations
 
 import ctypes as C
+import json
 import os
 
 import torch  # noqa: F401  (must precede CDLL, see module docstring)
@@ -21,6 +22,9 @@ LIB_PATH = os.environ.get("MI355X_VLLM_LIB") or os.path.join(_HERE, "csrc", "lib
 MI_F32, MI_BF16 = 0, 1
 MI_W = {"bfloat16": 0, "bf16": 0, None: 0, "f8e4m3": 1, "fp8": 1, "int8": 2}
 MI_Q = {"per_tensor_symmetric": 0, "per_channel_symmetric": 1}
+MI_KV = {"auto": 0, "bfloat16": 0, "fp8": 1, "fp8_e4m3": 1}    # vLLM cache_dtype -> mi_model_config.kv_cache_dtype
+KV_SCALE_SUFFIXES = ("self_attn.k_scale", "self_attn.v_scale")   # scalar fp32 per layer (vLLM checkpoint names)
+KV_SCALES_FILE = "kv_scales.json"                                 # beside the .miw images of an artifact directory
 K_CLASSES = ("gemv", "gemm", "attn_decode", "attn_prefill", "other", "comm")
 
 
@@ -38,6 +42,7 @@ class MiModelConfig(C.Structure):
         ("tp_degree", C.c_int32), ("tp_rank", C.c_int32), ("device_id", C.c_int32),
         ("use_graphs", C.c_int32), ("prefill_fp8_activations", C.c_int32),
         ("tp_device_ids", C.c_int32 * 16), ("tp_transport", C.c_int32),
+        ("kv_cache_dtype", C.c_int32),
     ]
 
 
@@ -127,6 +132,13 @@ _SIGS = {
     "mi_op_paged_attn_prefill": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                            C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_void_p, C.c_void_p]),
+    "mi_op_kv_write_f8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p]),
+    "mi_op_paged_attn_decode_f8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_op_kv_dequant_gather": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -188,6 +200,7 @@ class NativeModel:
         self.cfg = c
         self.vocab_size = c.vocab_size
         self._logits_view = None
+        self._kv_scales = {}
         self._ctx = C.c_void_p()
         check(self.lib.mi_ctx_create(C.byref(c), C.byref(self._ctx)))
 
@@ -204,6 +217,9 @@ class NativeModel:
 
     def load_weight(self, name: str, tensor: "torch.Tensor") -> None:
         t = tensor.detach().cpu().contiguous()
+        if name.endswith(KV_SCALE_SUFFIXES):     # FP8 KV scales are not part of the weight images: kept for save_artifacts
+            self._kv_scales[name] = float(t.reshape(-1)[0])
+            t = t.reshape(1)
         if t.dtype == torch.bfloat16:
             dt = MI_BF16
         else:
@@ -213,18 +229,26 @@ class NativeModel:
 
     def load_state_dict(self, weights: dict) -> None:
         for name, t in weights.items():
-            if t.dim() in (1, 2):
+            if t.dim() in (1, 2) or name.endswith(KV_SCALE_SUFFIXES):
                 self.load_weight(name, t)
 
     def save_artifacts(self, directory: str) -> None:
         """Write this context's device weight images (one file per rank) under `directory`."""
         os.makedirs(directory, exist_ok=True)
         check(self.lib.mi_save_weights(self._ctx, os.fsencode(directory)))
+        if self._kv_scales:                      # FP8 KV scales ride beside the images (they are not part of them)
+            with open(os.path.join(directory, KV_SCALES_FILE), "w", encoding="utf-8") as f:
+                json.dump(self._kv_scales, f)
 
     def load_artifacts(self, directory: str) -> None:
         """Load the device weight images saved by `save_artifacts`; ValueError when they are
         missing or were made for another configuration."""
         check(self.lib.mi_load_weights_file(self._ctx, os.fsencode(directory)))
+        path = os.path.join(directory, KV_SCALES_FILE)
+        if os.path.exists(path):                 # the .miw images hold no KV scales: re-send the ones saved beside them
+            with open(path, "r", encoding="utf-8") as f:
+                for name, val in json.load(f).items():
+                    self.load_weight(name, torch.tensor([val], dtype=torch.float32))
 
     def init_synthetic_weights(self, seed: int = 1, std: float = 0.02) -> None:
         check(self.lib.mi_init_synthetic_weights(self._ctx, seed, std))

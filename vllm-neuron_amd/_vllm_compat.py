@@ -648,6 +648,7 @@ class SimpleCacheConfig:
     enable_prefix_caching: bool = True
     num_gpu_blocks: Optional[int] = None
     num_cpu_blocks: Optional[int] = None
+    cache_dtype: str = "auto"    # "auto" / "bfloat16": bf16 KV pool; "fp8" / "fp8_e4m3": e4m3 pool with static scales
 
 
 @dataclass

@@ -9,6 +9,7 @@
 // i.e. one (block, kv-head) tile is a dense block_size*hd*2-byte range (8 KiB at 32 x 128),
 // which a wave streams as 1 KiB coalesced reads.  Block 0 is vLLM's null block
 // (reference platform.py:150-159): valid memory, never referenced by a live position.
+// The FP8 form of the pool (end of this header) is the same index with one-byte e4m3 elements.
 #pragma once
 #include "mi_common.h"
 
@@ -40,5 +41,22 @@ int launch_attn_prefill(const uint16_t* q, int T, int q_pos0, const uint16_t* kp
 // k, v [T, nkv, hd] bf16 -> pool at slots [T] (-1 skips)
 int launch_kv_write(const uint16_t* k, const uint16_t* v, const int64_t* slots, int T, int nkv, int hd,
                     uint16_t* kpool, uint16_t* vpool, int block_size, hipStream_t s);
+
+// ---- FP8 (OCP e4m3fn) pool: [num_blocks][nkv][block_size][hd] BYTES per K / V, static scales --------------------
+// write: code = rne_e4m3(clamp(float(x_bf16) * (1.0f / scale), -448, 448)); read: value = float(code) * scale.
+// k, v [T, nkv, hd] bf16 -> byte pool at slots [T] (-1 skips)
+int launch_kv_write_f8(const uint16_t* k, const uint16_t* v, const int64_t* slots, int T, int nkv, int hd, uint8_t* kpool,
+                       uint8_t* vpool, int block_size, float k_scale, float v_scale, hipStream_t s);
+// launch_attn_decode over the byte pool (same grid, splits, scratch layout and combine; no in-launch merge).
+// k_scale rides in the score scale, v_scale multiplies the merged output once; every MFMA is bf16.
+int launch_attn_decode_f8(const uint16_t* q, const uint8_t* kpool, const uint8_t* vpool, int block_size,
+                          const int32_t* block_table, int MB, const int32_t* ctx_lens, int B, int nh, int nkv, int hd,
+                          float k_scale, float v_scale, uint16_t* out, void* scratch, hipStream_t s, int rows_per_seq = 1,
+                          int num_blocks = 0);
+// One sequence's blocks 0 .. ceil(kv_len / block_size) - 1, in block-table order, widened to a bf16 pool
+// staged [2][nblk][nkv][block_size][hd] (element bf16_rne(float(code) * scale)) that launch_attn_prefill reads with an
+// identity block table.  pool: K bytes, then V bytes (num_blocks blocks each).
+int launch_kv_dequant_gather(const uint8_t* pool, int num_blocks, int block_size, const int32_t* block_table, int MB,
+                             int kv_len, int nkv, int hd, float k_scale, float v_scale, uint16_t* staged, hipStream_t s);
 
 }  // namespace mi

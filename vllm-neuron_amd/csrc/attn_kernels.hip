@@ -439,6 +439,265 @@ int launch_attn_decode(const uint16_t* q, const uint16_t* kpool, const uint16_t*
 }
 
 // =====================================================================================
+// token generation over an FP8 (e4m3) pool
+// =====================================================================================
+// The same grid, context-split dealing, partial layout and combine as attn_decode_kernel; what differs is how the
+// bytes travel.  A K/V row is HD BYTES, so a wave walks 64-token tiles (8 KiB of K + 8 KiB of V at head_dim 128: the
+// bytes of a bf16 32-token tile), two in flight: 2 x 16 KiB per wave at long context, as the bf16 kernel has.  A tile
+// is four 16-token groups that each look their own block up (block_size 16 / 32 / 48 ...), consumed as two 32-token
+// halves through the bf16 kernel's S^T / softmax / P.V step.  All MFMAs are v_mfma_f32_16x16x32_bf16: the codes are
+// widened to bf16 in registers (exact), q / P / the output keep their bf16 rounding points, k_scale rides in the
+// score scale and v_scale multiplies the wave-merged output once.
+//   K: lane (g, c) of a 16-token group loads 16 bytes of token c: dims 64 j + 16 g .. + 15 (j < HD / 64) with ONE
+//      global_load_dwordx4.  The 16 codes decode to two A fragments, so k-step 2 j + e of lane g covers dims
+//      64 j + 16 g + 8 e .. + 7; the q fragments are loaded once with the same map (a dot product does not care
+//      in which order the dimensions are summed as long as both operands agree).
+//   V: whole rows (lane-linear 16-byte chunks) parked as BYTES in a wave-private LDS tile, row pitch HD + 16.  Token
+//      32 h + 16 u + 4 g + i of the tile is parked at row 32 h + 8 g + 4 u + i, so the 8 k-slots of lane group g in
+//      half h -- bound to tokens 4 g + j (j < 4) and 16 + 4 g + j - 4, where the two S^T accumulators hold their
+//      scores -- are the 8 CONSECUTIVE rows 32 h + 8 g ..  ds_read_b64_tr_b8 then delivers the A operand whole:
+//      within a 16-lane group lane 2 r + p addresses row r, bytes 8 p .. 8 p + 7 of a 16-dim column block, and lane
+//      i receives byte i of the 8 rows = V^T[16 dn + i][k-slots 8 g .. 8 g + 7] (ONE transposed read per MFMA; the
+//      bf16 kernel needs two).  A half-wave reads 16 consecutive rows: 16 different 4-bank windows at this pitch.
+// Masking is by score (P = 0), so EVERY byte the kernel may fetch -- tokens past the context inside a live half, groups
+// read from the null block, the clamped early fetch -- must be a finite code: P = 0 times the e4m3 NaN code (0x7F / 0xFF)
+// would poison the accumulator.  The write rule saturates and the pool's owner zero-fills it, so the library's own pool
+// never holds one; a caller of mi_op_paged_attn_decode_f8 that owns its pool must keep that promise.
+typedef __attribute__((ext_vector_type(2))) int i32x2_t;
+
+template <int HD, int NW, bool FINAL>
+__global__ __launch_bounds__(NW * 64) void attn_decode_f8_kernel(
+    const uint16_t* __restrict__ q, const uint8_t* __restrict__ kpool, const uint8_t* __restrict__ vpool,
+    int bs, const int32_t* __restrict__ block_table, int MB, const int32_t* __restrict__ ctx_lens,
+    int nh, int nkv, int G, int NS, float* __restrict__ o_part, float* __restrict__ ml_part,
+    uint16_t* __restrict__ out, float score_scale, float v_scale, int R, int num_blocks) {
+  constexpr int TT = 64;            // tokens per tile
+  constexpr int KPB = HD + 16;      // LDS row pitch (bytes)
+  constexpr int CPR = HD / 16;      // 16-byte chunks per row
+  constexpr int KJ = HD / 64;       // 16-byte K loads per lane and 16-token group
+  constexpr int KS = HD / 32, DN = HD / 16;
+  constexpr int NK = 4 * KJ;        // 16-byte K loads per lane per tile
+  constexpr int NV = TT * CPR / 64; // 16-byte V loads per lane per tile
+  constexpr int VT = TT * KPB;      // bytes of one wave's V tile (>= the 16 x HD fp32 the wave merge parks there)
+  static_assert(VT >= 16 * HD * 4, "the wave merge reuses the V tile");
+  extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+  float* sm_ml = reinterpret_cast<float*>(dsm + (size_t)NW * VT);    // [NW][16][2]
+
+  const int split = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z * R;   // b: first batch row of the sequence
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int g = lane >> 4, c = lane & 15;
+  const int Gc = G * R;                         // live MFMA columns (see attn_decode_kernel for R > 1)
+  const int cr = c / G, ch = c - cr * G;
+  int ctx = 0;
+  for (int r = 0; r < R; ++r) ctx = max(ctx, ctx_lens[b + r]);
+  const int ctx_c = c < Gc ? ctx_lens[b + cr] : 0;
+  const int nt = ceil_div(ctx, TT), stride = NS * NW;
+  const int t_first = split * NW + wave, t_end = nt;
+  unsigned char* Vw = dsm + (size_t)wave * VT;
+
+  u32x4_t kA[NK], vA[NV], kB[NK], vB[NV];
+  // EARLY (num_blocks > 0, the wave's first tile only): no use of the context length; the table index and the block
+  // id are clamped into range, and what was fetched is masked by score or never consumed.  Otherwise a group beyond
+  // the context (and possibly beyond the table) reads the null block, a tile beyond the wave's range one line of it.
+  auto issue = [&](u32x4_t (&kr)[NK], u32x4_t (&vr)[NV], int tt, bool early) {
+    const bool live = early || tt < t_end;
+    const int tok0 = live ? tt * TT : 0;
+    size_t rowh[4];   // pool row of the first token of each 16-token group
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int tok = tok0 + 16 * u;
+      int blk;
+      bool in;
+      if (early) {
+        in = true;
+        blk = min(max(block_table[(size_t)b * MB + min(tok / bs, MB - 1)], 0), num_blocks - 1);
+      } else {
+        in = live && tok < ctx;
+        blk = in ? block_table[(size_t)b * MB + tok / bs] : 0;
+      }
+      rowh[u] = in ? ((size_t)blk * nkv + kvh) * bs + (tok % bs) : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const size_t kbase = live ? (rowh[u] + c) * HD + g * 16 : 0;
+#pragma unroll
+      for (int j = 0; j < KJ; ++j)
+        kr[u * KJ + j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(kpool + kbase + (live ? 64 * j : 0)));
+    }
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int row = (lane + 64 * i) / CPR, chn = (lane + 64 * i) % CPR;   // row of the tile, 16-byte chunk of the row
+      const size_t src = live ? (rowh[row >> 4] + (row & 15)) * HD + chn * 16 : 0;
+      vr[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(vpool + src));
+    }
+  };
+  issue(kA, vA, t_first, num_blocks > 0);
+
+  // q fragment (j, e) of lane (g, c): head column c, dims 64 j + 16 g + 8 e .. + 7
+  u32x4_t qf[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks)
+    qf[ks] = (c < Gc) ? *reinterpret_cast<const u32x4_t*>(q + ((size_t)(b + cr) * nh + kvh * G + ch) * HD + 64 * (ks >> 1) + 16 * g + 8 * (ks & 1))
+                      : u32x4_t{0, 0, 0, 0};
+  f32x4_t acc[DN];
+#pragma unroll
+  for (int dn = 0; dn < DN; ++dn) acc[dn] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float mrow = -INFINITY, lrow = 0.f;   // head c: running max (same on its 4 lanes), this lane's share of the sum
+  const int tr_off = (8 * g + (c >> 1)) * KPB + 8 * (c & 1);   // transposed read: row 8 g + c / 2, byte half c % 2
+
+  auto update = [&](const u32x4_t (&kr)[NK], const u32x4_t (&vr)[NV], int tt) {
+    // park V (the previous tile's transposed reads are complete: their values fed MFMAs already)
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int row = (lane + 64 * i) / CPR, chn = (lane + 64 * i) % CPR;
+      const int prow = (row & 32) | (((row >> 2) & 3) << 3) | (((row >> 4) & 1) << 2) | (row & 3);
+      *reinterpret_cast<u32x4_t*>(Vw + prow * KPB + chn * 16) = vr[i];
+    }
+    asm volatile("" ::: "memory");   // LDS ops of one wave execute in order; keep the compiler from reordering them
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int tok0 = tt * TT + 32 * h;
+      if (tok0 >= ctx) break;         // wave-uniform: the whole half lies beyond the context
+      f32x4_t st[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        st[u] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < KJ; ++j) {
+          const u32x4_t kw = kr[(2 * h + u) * KJ + j];
+          st[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(decode8<MI_W_F8E4M3>(kw[0], kw[1]), __builtin_bit_cast(bf16x8_t, qf[2 * j]), st[u], 0, 0, 0);
+          st[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(decode8<MI_W_F8E4M3>(kw[2], kw[3]), __builtin_bit_cast(bf16x8_t, qf[2 * j + 1]), st[u], 0, 0, 0);
+        }
+      }
+      i32x2_t vt[DN];
+#pragma unroll
+      for (int dn = 0; dn < DN; ++dn)
+        vt[dn] = __builtin_amdgcn_ds_read_tr8_b64_v2i32((i32x2_t __attribute__((address_space(3)))*)(Vw + 32 * h * KPB + tr_off + 16 * dn));
+      float pv[8];
+      float mx = -INFINITY;
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          float sv = st[u][i] * score_scale;
+          if (tok0 + 16 * u + 4 * g + i >= ctx_c) sv = -INFINITY;
+          pv[4 * u + i] = sv;
+          mx = fmaxf(mx, sv);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 16));
+      mx = fmaxf(mx, __shfl_xor(mx, 32));       // -inf where the column has no live token in this half (sexp2 conventions)
+      const float mn = fmaxf(mrow, mx);
+      const float alpha = sexp2(mrow, mn);
+      float ps = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        pv[k] = sexp2(pv[k], mn);
+        ps += pv[k];
+      }
+      const bool moved = mn != mrow;
+      mrow = mn;
+      lrow = lrow * alpha + ps;
+      union { uint32_t w[4]; bf16x8_t v; } pk;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) pk.w[k] = pack_bf16x2(pv[2 * k], pv[2 * k + 1]);
+      if (__any(moved)) {
+#pragma unroll
+        for (int dn = 0; dn < DN; ++dn) {
+          acc[dn][0] *= alpha; acc[dn][1] *= alpha; acc[dn][2] *= alpha; acc[dn][3] *= alpha;
+        }
+      }
+#pragma unroll
+      for (int dn = 0; dn < DN; ++dn)
+        acc[dn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(decode8<MI_W_F8E4M3>((uint32_t)vt[dn][0], (uint32_t)vt[dn][1]), pk.v, acc[dn], 0, 0, 0);
+    }
+  };
+
+  for (int tt = t_first; tt < t_end; tt += 2 * stride) {
+    issue(kB, vB, tt + stride, false);
+    update(kA, vA, tt);
+    issue(kA, vA, tt + 2 * stride, false);
+    if (tt + stride < t_end) update(kB, vB, tt + stride);
+  }
+
+  // ---- merge the waves: O^T / m / l of wave w go to its own (now idle) LDS tile --------------
+  lrow += __shfl_xor(lrow, 16);
+  lrow += __shfl_xor(lrow, 32);
+  asm volatile("" ::: "memory");
+  float* so = reinterpret_cast<float*>(Vw);            // [16 heads][HD] f32
+#pragma unroll
+  for (int dn = 0; dn < DN; ++dn) *reinterpret_cast<f32x4_t*>(&so[c * HD + 16 * dn + 4 * g]) = acc[dn];
+  if (g == 0) {
+    sm_ml[(wave * 16 + c) * 2] = mrow;
+    sm_ml[(wave * 16 + c) * 2 + 1] = lrow;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < Gc * HD; idx += NW * 64) {
+    const int h = idx / HD, d = idx % HD;       // h: MFMA column
+    const int hr = h / G, hh = h - hr * G;      // -> (row of the sequence, head)
+    float M = sm_ml[h * 2];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) M = fmaxf(M, sm_ml[(w * 16 + h) * 2]);
+    float o = 0.f, L = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {  // wave order: deterministic
+      const float f = sexp2(sm_ml[(w * 16 + h) * 2], M);
+      o += f * reinterpret_cast<const float*>(dsm + (size_t)w * VT)[h * HD + d];
+      L += f * sm_ml[(w * 16 + h) * 2 + 1];
+    }
+    if constexpr (FINAL) {
+      out[((size_t)(b + hr) * nh + kvh * G + hh) * HD + d] = f32_to_bf16(L > 0.f ? o / L * v_scale : 0.f);   // empty context -> zeros
+    } else {
+      const size_t row = ((size_t)(b + hr) * nh + kvh * G + hh) * kAttnMaxSplits + split;
+      o_part[row * HD + d] = o * v_scale;
+      if (d == 0) {
+        ml_part[row * 2] = M;
+        ml_part[row * 2 + 1] = L;
+      }
+    }
+  }
+}
+template <int HD, int NW>
+constexpr size_t attn_decode_f8_lds() { return (size_t)NW * 64 * (HD + 16) + (size_t)NW * 16 * 2 * sizeof(float); }
+
+template <int HD>
+static int launch_decode_f8_t(const uint16_t* q, const uint8_t* kpool, const uint8_t* vpool, int bs, const int32_t* bt,
+                              int MB, const int32_t* ctx, int B, int nh, int nkv, float k_scale, float v_scale,
+                              uint16_t* out, void* scratch, hipStream_t s, int R, int num_blocks) {
+  const int G = nh / nkv, Bs = B / R, NS = attn_decode_splits(Bs, nkv);   // Bs sequences of R batch rows each
+  float* ml_part = reinterpret_cast<float*>(reinterpret_cast<unsigned int*>(scratch) + kAttnTickets);
+  float* o_part = ml_part + (size_t)B * nh * kAttnMaxSplits * 2;
+  const float score_scale = 1.4426950408889634f / sqrtf((float)HD) * k_scale;
+  constexpr size_t lds8 = attn_decode_f8_lds<HD, 8>(), lds4 = attn_decode_f8_lds<HD, 4>();
+  MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_decode_f8_kernel<HD, 8, true>), (int)lds8));
+  MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_decode_f8_kernel<HD, 4, false>), (int)lds4));
+  if (NS == 1) {
+    hipLaunchKernelGGL((attn_decode_f8_kernel<HD, 8, true>), dim3(1, nkv, Bs), dim3(512), lds8, s, q, kpool, vpool, bs, bt,
+                       MB, ctx, nh, nkv, G, 1, nullptr, nullptr, out, score_scale, v_scale, R, num_blocks);
+  } else {
+    hipLaunchKernelGGL((attn_decode_f8_kernel<HD, 4, false>), dim3(NS, nkv, Bs), dim3(256), lds4, s, q, kpool, vpool, bs, bt,
+                       MB, ctx, nh, nkv, G, NS, o_part, ml_part, nullptr, score_scale, v_scale, R, num_blocks);
+    hipLaunchKernelGGL((attn_combine_kernel<HD>), dim3(nh, B), dim3(HD), 0, s, o_part, ml_part, NS, nh, out);
+  }
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+int launch_attn_decode_f8(const uint16_t* q, const uint8_t* kpool, const uint8_t* vpool, int block_size,
+                          const int32_t* block_table, int MB, const int32_t* ctx_lens, int B, int nh, int nkv, int hd,
+                          float k_scale, float v_scale, uint16_t* out, void* scratch, hipStream_t s, int rows_per_seq,
+                          int num_blocks) {
+  MI_CHECK(hd == 64 || hd == 128, "attention: head_dim must be 64 or 128");
+  MI_CHECK(rows_per_seq >= 1 && B % rows_per_seq == 0 && (nh / nkv) * rows_per_seq <= 16,
+           "attention: rows_per_seq must divide the batch and q heads per kv head x rows_per_seq must be <= 16");
+  MI_CHECK(nh % nkv == 0 && nh / nkv <= 16, "attention: q heads per kv head must be 1..16");
+  MI_CHECK(block_size % 16 == 0, "attention: block_size must be a multiple of 16");
+  MI_CHECK(MB >= 1 && k_scale > 0.f && v_scale > 0.f, "attention: the block table width and the FP8 KV scales must be positive");
+  if (hd == 128) return launch_decode_f8_t<128>(q, kpool, vpool, block_size, block_table, MB, ctx_lens, B, nh, nkv, k_scale, v_scale, out, scratch, s, rows_per_seq, num_blocks);
+  return launch_decode_f8_t<64>(q, kpool, vpool, block_size, block_table, MB, ctx_lens, B, nh, nkv, k_scale, v_scale, out, scratch, s, rows_per_seq, num_blocks);
+}
+
+// =====================================================================================
 // context encoding
 // =====================================================================================
 // One work-group per (32*QB queries, kv head): wave w owns q head (w % Gp) of the kv group and
@@ -1082,6 +1341,69 @@ int launch_kv_write(const uint16_t* k, const uint16_t* v, const int64_t* slots, 
   MI_CHECK(hd % 8 == 0, "kv_write: head_dim % 8 == 0 required");
   if (T == 0) return MI_OK;
   hipLaunchKernelGGL(kv_write_kernel, dim3(T), dim3(128), 0, s, k, v, slots, nkv, hd, kpool, vpool, block_size);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+// ---- FP8 pool: the write rule of mi_common.h (kv_quant4) per 4 values, one 4-byte store each --------------------
+__global__ void kv_write_f8_kernel(const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,
+                                   const int64_t* __restrict__ slots, int nkv, int hd, uint8_t* __restrict__ kpool,
+                                   uint8_t* __restrict__ vpool, int bs, float k_inv, float v_inv) {
+  const int t = blockIdx.x;
+  const long slot = slots[t];
+  if (slot < 0) return;
+  const int blk = (int)(slot / bs), off = (int)(slot % bs);
+  const int quads = nkv * hd / 4;
+  for (int i = threadIdx.x; i < quads; i += blockDim.x) {
+    const int head = (i * 4) / hd, d = (i * 4) % hd;
+    const size_t dst = (((size_t)blk * nkv + head) * bs + off) * hd + d;
+    *reinterpret_cast<uint32_t*>(kpool + dst) = kv_quant4(*reinterpret_cast<const uint2*>(k + (size_t)t * nkv * hd + i * 4), k_inv);
+    *reinterpret_cast<uint32_t*>(vpool + dst) = kv_quant4(*reinterpret_cast<const uint2*>(v + (size_t)t * nkv * hd + i * 4), v_inv);
+  }
+}
+
+int launch_kv_write_f8(const uint16_t* k, const uint16_t* v, const int64_t* slots, int T, int nkv, int hd, uint8_t* kpool,
+                       uint8_t* vpool, int block_size, float k_scale, float v_scale, hipStream_t s) {
+  MI_CHECK(hd % 16 == 0, "kv_write_f8: head_dim % 16 == 0 required");
+  MI_CHECK(k_scale > 0.f && v_scale > 0.f, "kv_write_f8: FP8 KV scales must be positive");
+  if (T == 0) return MI_OK;
+  hipLaunchKernelGGL(kv_write_f8_kernel, dim3(T), dim3(128), 0, s, k, v, slots, nkv, hd, kpool, vpool, block_size,
+                     1.0f / k_scale, 1.0f / v_scale);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+// ---- FP8 pool -> bf16 staging pool for context encoding ---------------------------------------------------------
+// The blocks of ONE sequence, in block-table order: staged [2][nblk][nkv][bs][hd] bf16 = bf16_rne(float(code) * scale).
+// A (block, all heads) range is contiguous in both pools, so a thread widens 16 codes (one 16-byte load, two 16-byte
+// stores); grid (chunks of a block, nblk, K / V).  Whole blocks are staged: the tail of the last one is finite pool
+// content that the attention kernel masks.
+__global__ __launch_bounds__(256) void kv_dequant_gather_kernel(const uint8_t* __restrict__ pool, size_t half_bytes,
+                                                                int num_blocks, int blk_bytes,
+                                                                const int32_t* __restrict__ block_table, int nblk,
+                                                                float k_scale, float v_scale, uint16_t* __restrict__ staged) {
+  const int chunk = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y, kv = blockIdx.z;
+  if (chunk * 16 >= blk_bytes) return;
+  const int blk = min(max(block_table[i], 0), num_blocks - 1);
+  const float scale = kv ? v_scale : k_scale;
+  const u32x4_t cw = *reinterpret_cast<const u32x4_t*>(pool + kv * half_bytes + (size_t)blk * blk_bytes + (size_t)chunk * 16);
+  uint16_t* dst = staged + ((size_t)kv * nblk + i) * blk_bytes + (size_t)chunk * 16;
+  u32x4_t lo, hi;
+  lo[0] = kv_dequant2_bf16(cw[0], false, scale); lo[1] = kv_dequant2_bf16(cw[0], true, scale);
+  lo[2] = kv_dequant2_bf16(cw[1], false, scale); lo[3] = kv_dequant2_bf16(cw[1], true, scale);
+  hi[0] = kv_dequant2_bf16(cw[2], false, scale); hi[1] = kv_dequant2_bf16(cw[2], true, scale);
+  hi[2] = kv_dequant2_bf16(cw[3], false, scale); hi[3] = kv_dequant2_bf16(cw[3], true, scale);
+  *reinterpret_cast<u32x4_t*>(dst) = lo;
+  *reinterpret_cast<u32x4_t*>(dst + 8) = hi;
+}
+
+int launch_kv_dequant_gather(const uint8_t* pool, int num_blocks, int block_size, const int32_t* block_table, int MB,
+                             int kv_len, int nkv, int hd, float k_scale, float v_scale, uint16_t* staged, hipStream_t s) {
+  MI_CHECK(hd % 16 == 0 && num_blocks >= 1 && block_size >= 1 && nkv >= 1, "kv_dequant_gather: bad pool geometry");
+  MI_CHECK(kv_len >= 1 && ceil_div(kv_len, block_size) <= MB, "kv_dequant_gather: block_table narrower than the context");
+  const int nblk = ceil_div(kv_len, block_size), blk_bytes = nkv * block_size * hd;
+  hipLaunchKernelGGL(kv_dequant_gather_kernel, dim3(ceil_div(blk_bytes / 16, 256), nblk, 2), dim3(256), 0, s, pool,
+                     (size_t)num_blocks * blk_bytes, num_blocks, blk_bytes, block_table, nblk, k_scale, v_scale, staged);
   MI_HIP(hipGetLastError());
   return MI_OK;
 }

@@ -7,7 +7,7 @@
 namespace mi {
 
 // What happens to the fp32 accumulator tile D[n][m] once the contraction is done.
-enum { EPI_F32 = 0, EPI_QKV = 1, EPI_SWIGLU = 2, EPI_RESID = 3 };
+enum { EPI_F32 = 0, EPI_QKV = 1, EPI_SWIGLU = 2, EPI_RESID = 3, EPI_QKV_F8 = 4 };   // QKV_F8: EPI_QKV into an e4m3 byte pool
 // Where the bf16 activations come from.
 enum { PRO_BF16 = 0, PRO_NORM = 1, PRO_NORM_PARTIAL = 2 };  // callers pass PRO_BF16 / PRO_NORM; PARTIAL is picked when ProArgs::partial is set
 
@@ -34,6 +34,9 @@ struct EpiArgs {
   // EPI_SWIGLU: rows interleaved (gate_i, up_i); act[m * ld_act + i] = silu(gate)*up
   uint16_t* act_out;
   int ld_act;
+  // EPI_QKV_F8: kpool / vpool are byte pools (same index, one-byte elements); 1.0f / k_scale, 1.0f / v_scale of the layer.
+  // (last, so that the kernel arguments of every other epilogue keep their offsets)
+  float k_inv, v_inv;
 };
 
 struct ProArgs {

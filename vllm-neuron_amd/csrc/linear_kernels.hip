@@ -84,7 +84,7 @@ __device__ __forceinline__ void epilogue_store(const EpiArgs& e, int m, int n0, 
     const float a1 = v[2] / (1.f + __expf(-v[2])) * v[3];
     *reinterpret_cast<uint32_t*>(e.act_out + (size_t)m * e.ld_act + (n0 >> 1)) =
         pack_bf16x2(a0, a1);
-  } else {  // EPI_QKV
+  } else {  // EPI_QKV, EPI_QKV_F8
     const int qk_end = e.q_dim + e.kv_dim;
     if (n0 < qk_end) {  // rotary: (v0,v1) and (v2,v3) are (d, d + hd/2) pairs
       const int j = (n0 < e.q_dim ? n0 : n0 - e.q_dim) % e.hd;
@@ -106,7 +106,11 @@ __device__ __forceinline__ void epilogue_store(const EpiArgs& e, int m, int n0, 
         const int head = rel / e.hd, d = rel % e.hd;
         const int blk = slot / e.block_size, off = slot % e.block_size;
         uint16_t* pool = is_k ? e.kpool : e.vpool;
-        *reinterpret_cast<uint2*>(pool + (((size_t)blk * e.nkv + head) * e.block_size + off) * e.hd + d) = packed;
+        const size_t at = (((size_t)blk * e.nkv + head) * e.block_size + off) * e.hd + d;
+        if constexpr (EPI == EPI_QKV_F8)   // byte pool: the write rule of mi_common.h, one 4-byte store
+          *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(pool) + at) = kv_quant4(packed, is_k ? e.k_inv : e.v_inv);
+        else
+          *reinterpret_cast<uint2*>(pool + at) = packed;
       }
     }
   }
@@ -119,13 +123,14 @@ __device__ __forceinline__ void epilogue_store(const EpiArgs& e, int m, int n0, 
 template <int EPI> struct EpiPre {};
 template <> struct EpiPre<EPI_RESID> { float4 r; };
 template <> struct EpiPre<EPI_QKV> { float2 cs, sn; int pos, slot; };
+template <> struct EpiPre<EPI_QKV_F8> : EpiPre<EPI_QKV> {};
 
 // independent loads (requested with the kernel's first operands) ...
 template <int EPI>
 __device__ __forceinline__ void epi_prefetch(const EpiArgs& e, int m, int n0, EpiPre<EPI>& p) {
   if constexpr (EPI == EPI_RESID) {
     p.r = *reinterpret_cast<const float4*>(e.resid_in + (size_t)m * e.ld_out + n0);
-  } else if constexpr (EPI == EPI_QKV) {
+  } else if constexpr (EPI == EPI_QKV || EPI == EPI_QKV_F8) {
     p.pos = e.pos[m];
     p.slot = e.slots[m];
   }
@@ -134,7 +139,7 @@ __device__ __forceinline__ void epi_prefetch(const EpiArgs& e, int m, int n0, Ep
 // has long arrived, and nothing waits for these before the last weight batch)
 template <int EPI>
 __device__ __forceinline__ void epi_prefetch_dependent(const EpiArgs& e, int n0, EpiPre<EPI>& p) {
-  if constexpr (EPI == EPI_QKV) {
+  if constexpr (EPI == EPI_QKV || EPI == EPI_QKV_F8) {
     const int qk_end = e.q_dim + e.kv_dim;
     const int nn = n0 < qk_end ? n0 : 0;                      // V columns: any valid table entry
     const int j = (nn < e.q_dim ? nn : nn - e.q_dim) % e.hd;
@@ -148,7 +153,7 @@ __device__ __forceinline__ void epi_prefetch_dependent(const EpiArgs& e, int n0,
 template <int EPI>
 __device__ __forceinline__ void epilogue_pre(const EpiArgs& e, int m, int n0, const float* sc4, const float* b4,
                                              f32x4_t v, const EpiPre<EPI>& p, float rmul = 1.f) {
-  if constexpr (EPI == EPI_RESID || EPI == EPI_QKV) {
+  if constexpr (EPI == EPI_RESID || EPI == EPI_QKV || EPI == EPI_QKV_F8) {
     const float4 sc = *reinterpret_cast<const float4*>(sc4);
     v[0] *= sc.x * rmul; v[1] *= sc.y * rmul; v[2] *= sc.z * rmul; v[3] *= sc.w * rmul;
     if (b4) {
@@ -174,7 +179,11 @@ __device__ __forceinline__ void epilogue_pre(const EpiArgs& e, int m, int n0, co
         const int head = rel / e.hd, d = rel % e.hd;
         const int blk = p.slot / e.block_size, off = p.slot % e.block_size;
         uint16_t* pool = is_k ? e.kpool : e.vpool;
-        *reinterpret_cast<uint2*>(pool + (((size_t)blk * e.nkv + head) * e.block_size + off) * e.hd + d) = packed;
+        const size_t at = (((size_t)blk * e.nkv + head) * e.block_size + off) * e.hd + d;
+        if constexpr (EPI == EPI_QKV_F8)   // byte pool: the write rule of mi_common.h, one 4-byte store
+          *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(pool) + at) = kv_quant4(packed, is_k ? e.k_inv : e.v_inv);
+        else
+          *reinterpret_cast<uint2*>(pool + at) = packed;
       }
     }
   } else {
@@ -594,7 +603,8 @@ __device__ __forceinline__ void pin_gemv_args(const uint4* W, int NT, int KT, in
   if constexpr (EPI == EPI_F32 || EPI == EPI_RESID) { pin_sgpr(e.out_f32); pin_sgpr(e.ld_out); }
   if constexpr (EPI == EPI_RESID) pin_sgpr(e.resid_in);
   if constexpr (EPI == EPI_SWIGLU) { pin_sgpr(e.act_out); pin_sgpr(e.ld_act); }
-  if constexpr (EPI == EPI_QKV) {
+  if constexpr (EPI == EPI_QKV_F8) { pin_sgpr(e.k_inv); pin_sgpr(e.v_inv); }
+  if constexpr (EPI == EPI_QKV || EPI == EPI_QKV_F8) {
     pin_sgpr(e.q_out); pin_sgpr(e.q_dim); pin_sgpr(e.kv_dim); pin_sgpr(e.hd); pin_sgpr(e.nkv); pin_sgpr(e.pos);
     pin_sgpr(e.slots); pin_sgpr(e.rope_cos); pin_sgpr(e.rope_sin); pin_sgpr(e.kpool); pin_sgpr(e.vpool);
     pin_sgpr(e.block_size);
@@ -1515,10 +1525,12 @@ static int launch_gemv_wd(const LinearW& w, int M, int pro, const ProArgs& p, in
     if (epi == EPI_F32) return launch_gemv_t<WD, PRO_BF16, EPI_F32>(w, M, p, e, s);
   } else if (p.partial) {
     if (epi == EPI_QKV) return launch_gemv_t<WD, PRO_NORM_PARTIAL, EPI_QKV>(w, M, p, e, s);
+    if (epi == EPI_QKV_F8) return launch_gemv_t<WD, PRO_NORM_PARTIAL, EPI_QKV_F8>(w, M, p, e, s);
     if (epi == EPI_SWIGLU) return launch_gemv_t<WD, PRO_NORM_PARTIAL, EPI_SWIGLU>(w, M, p, e, s);
     if (epi == EPI_F32) return launch_gemv_t<WD, PRO_NORM_PARTIAL, EPI_F32>(w, M, p, e, s);
   } else {
     if (epi == EPI_QKV) return launch_gemv_t<WD, PRO_NORM, EPI_QKV>(w, M, p, e, s);
+    if (epi == EPI_QKV_F8) return launch_gemv_t<WD, PRO_NORM, EPI_QKV_F8>(w, M, p, e, s);
     if (epi == EPI_SWIGLU) return launch_gemv_t<WD, PRO_NORM, EPI_SWIGLU>(w, M, p, e, s);
     if (epi == EPI_F32) return launch_gemv_t<WD, PRO_NORM, EPI_F32>(w, M, p, e, s);
   }
@@ -1696,6 +1708,7 @@ static int launch_gemm_wd(const LinearW& w, int T, const uint16_t* x, int ldx, i
     } \
   } while (0)
   if (epi == EPI_QKV) MI_G(EPI_QKV);
+  else if (epi == EPI_QKV_F8) MI_G(EPI_QKV_F8);
   else if (epi == EPI_SWIGLU) MI_G(EPI_SWIGLU);
   else if (epi == EPI_RESID) MI_G(EPI_RESID);
   else MI_G(EPI_F32);
@@ -1880,6 +1893,7 @@ static int launch_gemm_wide_bm(const LinearW& w, int T, const uint16_t* x, int l
     } \
   } while (0)
   if (epi == EPI_QKV) MI_GW(EPI_QKV);
+  else if (epi == EPI_QKV_F8) MI_GW(EPI_QKV_F8);
   else if (epi == EPI_SWIGLU) MI_GW(EPI_SWIGLU);
   else if (epi == EPI_RESID) MI_GW(EPI_RESID);
   else MI_GW(EPI_F32);
@@ -2321,6 +2335,7 @@ int launch_gemm_a8(const LinearW& w, int T, const uint8_t* x8, int ldx, int epi,
     } \
   } while (0)
       if (epi == EPI_QKV) MI_A8W(EPI_QKV);
+  else if (epi == EPI_QKV_F8) MI_A8W(EPI_QKV_F8);
       else if (epi == EPI_SWIGLU) MI_A8W(EPI_SWIGLU);
       else if (epi == EPI_RESID) MI_A8W(EPI_RESID);
       else MI_A8W(EPI_F32);
@@ -2355,6 +2370,7 @@ int launch_gemm_a8(const LinearW& w, int T, const uint8_t* x8, int ldx, int epi,
     } \
   } while (0)
   if (epi == EPI_QKV) MI_A8(EPI_QKV);
+  else if (epi == EPI_QKV_F8) MI_A8(EPI_QKV_F8);
   else if (epi == EPI_SWIGLU) MI_A8(EPI_SWIGLU);
   else if (epi == EPI_RESID) MI_A8(EPI_RESID);
   else MI_A8(EPI_F32);

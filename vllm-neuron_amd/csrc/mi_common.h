@@ -125,6 +125,22 @@ __device__ __forceinline__ uint32_t f32_to_e4m3fn(float f) {
   return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(c, 0.f, 0, false) & 0xffu;
 }
 
+// FP8 KV cache, write rule: four bf16-rounded K (or V) values of one row -> four e4m3 codes (one 4-byte store).
+// code = rne_e4m3(clamp(float(x_bf16) * inv, -448, 448)), inv = 1.0f / scale computed once on the host.  Every writer
+// of the byte pool goes through this function, so the stand-alone write and a GEMM epilogue give the same bytes.
+__device__ __forceinline__ uint32_t kv_quant4(uint2 bf16x4, float inv) {
+  float f[4] = {bf16lo_to_f32(bf16x4.x) * inv, bf16hi_to_f32(bf16x4.x) * inv, bf16lo_to_f32(bf16x4.y) * inv,
+                bf16hi_to_f32(bf16x4.y) * inv};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) f[i] = __builtin_fminf(__builtin_fmaxf(f[i], -448.f), 448.f);   // NaN -> -448: no NaN code
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
+  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
+}
+// read rule: value = float(code) * scale (e4m3 -> fp32 is exact); here for the two codes in the low / high half of a word
+__device__ __forceinline__ uint32_t kv_dequant2_bf16(uint32_t codes, bool hi, float scale) {
+  const f32x2_t v = hi ? __builtin_amdgcn_cvt_pk_f32_fp8(codes, true) : __builtin_amdgcn_cvt_pk_f32_fp8(codes, false);
+  return pack_bf16x2(v[0] * scale, v[1] * scale);
+}
 
 // ---- weight stream primitives -----------------------------------------------------------
 // MI_STREAM_ASM = 0 (default): plain non-temporal loads; hipcc owns the s_waitcnt placement.

@@ -247,8 +247,18 @@ int run_layers(mi_ctx* c, int rows, bool decode, int B, int MB, int q_pos0, int 
   bool have_partial = false;
   for (int l = 0; l < k.num_layers; ++l) {
     const LayerW& W = c->layers[l];
-    uint16_t* kpool = c->kv_pool + (size_t)l * 2 * c->kv_half;
-    uint16_t* vpool = kpool + c->kv_half;
+    const bool f8 = c->kv_f8();   // byte pool: the same index, one-byte elements
+    uint16_t* kpool = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(c->kv_pool) + (size_t)l * 2 * c->kv_half * c->kv_esz());
+    uint16_t* vpool = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(kpool) + c->kv_half * c->kv_esz());
+    const uint8_t *kpool8 = reinterpret_cast<const uint8_t*>(kpool), *vpool8 = reinterpret_cast<const uint8_t*>(vpool);
+    const float ksc = c->k_scale[l], vsc = c->v_scale[l];
+    // FP8 KV, context encoding: stage the sequence's keys 0 .. kv_len - 1 as bf16, then the bf16 kernel with the identity table
+    auto prefill_f8 = [&](const uint16_t* qp, int n, int pos0, const int32_t* bt, uint16_t* outp) -> int {
+      const int nblk = ceil_div(pos0 + n, k.block_size);
+      MI_TRY(launch_kv_dequant_gather(kpool8, k.num_blocks, k.block_size, bt, MB, pos0 + n, c->nkv_l, c->hd, ksc, vsc, c->kv_stage, s));
+      return launch_attn_prefill(qp, n, pos0, c->kv_stage, c->kv_stage + (size_t)nblk * c->nkv_l * k.block_size * c->hd,
+                                 k.block_size, c->d_ident, c->nh_l, c->nkv_l, c->hd, outp, s);
+    };
     {  // norm -> QKV -> RoPE -> q / KV pool
       ProArgs p{};
       p.resid_in = c->resid[cur];
@@ -260,13 +270,18 @@ int run_layers(mi_ctx* c, int rows, bool decode, int B, int MB, int q_pos0, int 
       e.q_out = c->qbuf; e.q_dim = c->q_dim; e.kv_dim = c->kv_dim; e.hd = c->hd; e.nkv = c->nkv_l;
       e.pos = c->d_pos; e.slots = c->d_slots; e.rope_cos = c->rope_cos; e.rope_sin = c->rope_sin;
       e.kpool = kpool; e.vpool = vpool; e.block_size = k.block_size;
-      MI_TRY(run_linear(c, W.qkv, rows, PRO_NORM, p, EPI_QKV, e));
+      e.k_inv = 1.0f / ksc; e.v_inv = 1.0f / vsc;
+      MI_TRY(run_linear(c, W.qkv, rows, PRO_NORM, p, f8 ? EPI_QKV_F8 : EPI_QKV, e));
       if (have_partial) cur ^= 1;
     }
     if (decode && !c->runs(MI_K_ATTN_DECODE)) {
       // (class-masked replay: see mi_replay_decode_classes)
     } else if (decode) {
       Scope sc(c, MI_K_ATTN_DECODE);
+      if (f8) MI_TRY(launch_attn_decode_f8(c->qbuf, kpool8, vpool8, k.block_size, c->d_bt, MB, c->d_ctx, B, c->nh_l, c->nkv_l, c->hd,
+                                           ksc, vsc, c->attn_out, c->attn_scratch, s, c->attn_rows_per_seq,
+                                           attn_early_kv() ? k.num_blocks : 0));
+      else
       MI_TRY(launch_attn_decode(c->qbuf, kpool, vpool, k.block_size, c->d_bt, MB, c->d_ctx, B, c->nh_l,
                                 c->nkv_l, c->hd, c->attn_out, c->attn_scratch, s, /*tickets_zeroed=*/true,
                                 c->attn_rows_per_seq, attn_early_kv() ? k.num_blocks : 0));
@@ -279,6 +294,11 @@ int run_layers(mi_ctx* c, int rows, bool decode, int B, int MB, int q_pos0, int 
         if (j > i) {
           // a run of requests that generate (one token each, consecutive rows and table rows): ONE split-context
           // decode-attention launch for all of them instead of a one-query context encoding per request
+          if (f8) MI_TRY(launch_attn_decode_f8(c->qbuf + (size_t)segs[i].row0 * c->q_dim, kpool8, vpool8, k.block_size,
+                                               c->d_bt + (size_t)i * MB, MB, c->d_seg_ctx + i, j - i, c->nh_l, c->nkv_l, c->hd, ksc, vsc,
+                                               c->attn_out + (size_t)segs[i].row0 * c->q_dim, c->attn_scratch, s, 1,
+                                               attn_early_kv() ? k.num_blocks : 0));
+          else
           MI_TRY(launch_attn_decode(c->qbuf + (size_t)segs[i].row0 * c->q_dim, kpool, vpool, k.block_size,
                                     c->d_bt + (size_t)i * MB, MB, c->d_seg_ctx + i, j - i, c->nh_l, c->nkv_l, c->hd,
                                     c->attn_out + (size_t)segs[i].row0 * c->q_dim, c->attn_scratch, s, false, 1,
@@ -286,6 +306,9 @@ int run_layers(mi_ctx* c, int rows, bool decode, int B, int MB, int q_pos0, int 
           i = j;
           continue;
         }
+        if (f8) MI_TRY(prefill_f8(c->qbuf + (size_t)segs[i].row0 * c->q_dim, segs[i].n, segs[i].pos0, c->d_bt + (size_t)i * MB,
+                                  c->attn_out + (size_t)segs[i].row0 * c->q_dim));
+        else
         MI_TRY(launch_attn_prefill(c->qbuf + (size_t)segs[i].row0 * c->q_dim, segs[i].n, segs[i].pos0, kpool, vpool,
                                    k.block_size, c->d_bt + (size_t)i * MB, c->nh_l, c->nkv_l, c->hd,
                                    c->attn_out + (size_t)segs[i].row0 * c->q_dim, s));
@@ -293,6 +316,8 @@ int run_layers(mi_ctx* c, int rows, bool decode, int B, int MB, int q_pos0, int 
       }
     } else {
       Scope sc(c, MI_K_ATTN_PREFILL);
+      if (f8) MI_TRY(prefill_f8(c->qbuf, rows, q_pos0, c->d_bt, c->attn_out));
+      else
       MI_TRY(launch_attn_prefill(c->qbuf, rows, q_pos0, kpool, vpool, k.block_size, c->d_bt, c->nh_l,
                                  c->nkv_l, c->hd, c->attn_out, s));
     }
@@ -576,7 +601,7 @@ int capture_or_launch_decode(mi_ctx* c, int B, int MB) {
 extern "C" {
 
 const char* mi_last_error(void) { return mi::g_err.c_str(); }
-int mi_version(void) { return 4; }   // 3: + in-process tensor parallelism (tp_rank = MI_TP_ALL_RANKS, tp_device_ids, tp_transport)
+int mi_version(void) { return 5; }   // 5: + kv_cache_dtype, mi_op_kv_write_f8 / mi_op_paged_attn_decode_f8 / mi_op_kv_dequant_gather; 4: + mi_tp_plan, mi_tp_info; 3: + in-process tensor parallelism (tp_rank = MI_TP_ALL_RANKS, tp_device_ids, tp_transport)
 
 int mi_tp_plan(const mi_model_config* cfg, int32_t rank, mi_tp_plan_t* out) {
   MI_CHECK(cfg && out, "null argument");
@@ -642,6 +667,7 @@ int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out) {
            "max_model_len spans more than 4096 blocks per sequence: raise block_size (context encoding stages a sequence's block table in LDS)");
   MI_CHECK(k.weight_dtype >= MI_W_BF16 && k.weight_dtype <= MI_W_INT8, "weight_dtype");
   MI_CHECK(k.quant_type == MI_Q_PER_TENSOR_SYMMETRIC || k.quant_type == MI_Q_PER_CHANNEL_SYMMETRIC, "quant_type");
+  MI_CHECK(k.kv_cache_dtype == MI_KV_BF16 || k.kv_cache_dtype == MI_KV_F8E4M3, "kv_cache_dtype");
   int ndev = 0;
   MI_HIP(hipGetDeviceCount(&ndev));
   MI_CHECK(ndev > 0, "no HIP device: this library has no CPU fallback");
@@ -678,6 +704,8 @@ int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out) {
 
   const int wd = k.weight_dtype;
   c->layers.resize(k.num_layers);
+  c->k_scale.assign(k.num_layers, 1.0f);
+  c->v_scale.assign(k.num_layers, 1.0f);
   for (auto& W : c->layers) {
     MI_TRY(alloc_linear(c, W.qkv, c->q_dim + 2 * c->kv_dim, c->H, wd, k.qkv_bias != 0));
     MI_TRY(alloc_linear(c, W.o, c->H, c->q_dim, wd, false));
@@ -715,7 +743,7 @@ int mi_ctx_destroy(mi_ctx* c) {
   fl(c->lm_head);
   void* ptrs[] = {c->g_final, c->embed, c->rowmax, c->kv_pool, c->rope_cos, c->rope_sin, c->stage_raw, c->stage_f32,
                   c->resid[0], c->resid[1], c->partial, c->xn, c->qbuf, c->attn_out, c->act, c->logits, c->logits_all,
-                  c->attn_scratch, c->d_inputs, c->d_dec, c->d_dec_bt, c->d_sparams, c->d_tokens, c->x8, c->x8_scale, c->splitk_ws, c->d_spec, c->d_sample_scratch};
+                  c->attn_scratch, c->kv_stage, c->d_ident, c->d_inputs, c->d_dec, c->d_dec_bt, c->d_sparams, c->d_tokens, c->x8, c->x8_scale, c->splitk_ws, c->d_spec, c->d_sample_scratch};
   for (void* p : ptrs) hipFree(p);
   void* hptrs[] = {c->h_inputs, c->h_dec, c->h_dec_bt, c->h_sparams, c->h_tokens, c->h_logits, c->h_spec};
   for (void* p : hptrs) if (p) hipHostFree(p);
@@ -728,8 +756,23 @@ int mi_load_weight(mi_ctx* c, const char* name_c, const void* host, int32_t dtyp
   MI_CHECK(c && name_c && host && shape, "null argument");
   if (c->owned_group)
     return group_run(c->owned_group, [&](mi_ctx* rc, int) { return mi_load_weight(rc, name_c, host, dtype, shape, ndim); });
-  MI_CHECK(!c->finalized, "mi_load_weight after mi_finalize");
   MI_CHECK(dtype == MI_F32 || dtype == MI_BF16, "weights must be fp32 or bf16 on the host");
+  {  // FP8 KV scales (vLLM checkpoint names): host state only, so legal after mi_finalize too, until a step has been captured
+    const bool ks = ends_with(name_c, "self_attn.k_scale"), vs = ends_with(name_c, "self_attn.v_scale");
+    if (ks || vs) {
+      int l = -1;
+      size_t numel = 1;
+      for (int i = 0; i < ndim; ++i) numel *= (size_t)shape[i];
+      MI_CHECK(ndim >= 0 && ndim <= 2 && numel == 1, "k_scale / v_scale must be scalars");
+      const float val = dtype == MI_F32 ? *reinterpret_cast<const float*>(host) : bf16_bits_to_f32(*reinterpret_cast<const uint16_t*>(host));
+      MI_CHECK(val > 0.f && val < INFINITY, "k_scale / v_scale must be positive and finite");
+      if (!c->kv_f8() || sscanf(name_c, "model.layers.%d.", &l) != 1 || l < 0 || l >= c->cfg.num_layers) return MI_OK;   // bf16 KV: accepted, ignored
+      MI_CHECK(c->graphs.empty(), "k_scale / v_scale after the first token-generation step");
+      (ks ? c->k_scale : c->v_scale)[l] = val;
+      return MI_OK;
+    }
+  }
+  MI_CHECK(!c->finalized, "mi_load_weight after mi_finalize");
   MI_CHECK(ndim == 1 || ndim == 2, "weights must be 1-D or 2-D");
   MI_HIP(hipSetDevice(c->cfg.device_id));
   const std::string name(name_c);
@@ -936,6 +979,9 @@ int mi_set_num_blocks(mi_ctx* c, int32_t num_blocks) {
 
 // bytes mi_finalize allocates besides the KV pool (activations, exchange buffers, scratch): what
 // has to be kept out of the memory offered to vLLM for KV blocks
+static size_t kv_stage_elems(const mi_ctx* c) {   // [2][blocks of max_model_len][nkv_l][bs][hd]
+  return 2 * (size_t)ceil_div(c->cfg.max_model_len, c->cfg.block_size) * c->nkv_l * c->cfg.block_size * c->hd;
+}
 static size_t workspace_estimate(const mi_ctx* c) {
   const mi_model_config& k = c->cfg;
   const size_t R = (size_t)c->max_rows, H = (size_t)c->H;
@@ -945,6 +991,7 @@ static size_t workspace_estimate(const mi_ctx* c) {
   b += (size_t)k.max_num_seqs * c->V_l * 4 * (1 + (k.tp_degree > 1 ? k.tp_degree : 0));
   b += attn_scratch_bytes(k.max_num_seqs, c->nh_l, c->hd);
   b += (size_t)k.max_model_len * c->hd * 4;                                 // rotary tables
+  if (c->kv_f8()) b += kv_stage_elems(c) * 2 + (size_t)ceil_div(k.max_model_len, k.block_size) * 4;   // FP8 KV: bf16 staging of one sequence
   if (k.tp_degree > 1) b += 8 * R * H + 4 * (R * H / k.tp_degree + 1024);   // exchange slots (tp_group.hip)
   return b + ((size_t)8 << 20);                                             // inputs, small buffers
 }
@@ -952,7 +999,7 @@ static size_t workspace_estimate(const mi_ctx* c) {
 int64_t mi_kv_bytes_per_block(mi_ctx* c) {
   if (!c) return 0;
   if (c->owned_group) c = c->owned_group->ranks[0];
-  return (int64_t)c->cfg.num_layers * 2 * c->nkv_l * c->cfg.block_size * c->hd * 2;
+  return (int64_t)c->cfg.num_layers * 2 * c->nkv_l * c->cfg.block_size * c->hd * (int64_t)c->kv_esz();
 }
 
 int mi_finalize(mi_ctx* c) {
@@ -979,17 +1026,26 @@ int mi_finalize(mi_ctx* c) {
   {
     size_t fr = 0, tot = 0;
     MI_HIP(hipMemGetInfo(&fr, &tot));
-    const size_t want = kv_elems * 2 + workspace_estimate(c);
+    const size_t want = kv_elems * c->kv_esz() + workspace_estimate(c);
     if (want > fr) {
-      set_error("KV pool of " + std::to_string(k.num_blocks) + " blocks (" + std::to_string(kv_elems * 2 >> 20) + " MiB over " +
+      set_error("KV pool of " + std::to_string(k.num_blocks) + " blocks (" + std::to_string(kv_elems * c->kv_esz() >> 20) + " MiB over " +
                 std::to_string(k.num_layers) + " layers) + " + std::to_string(workspace_estimate(c) >> 20) +
                 " MiB of workspace do not fit the " + std::to_string(fr >> 20) + " MiB free on the device: lower "
                 "num_gpu_blocks_override / gpu_memory_utilization");
       return MI_ENOMEM;
     }
   }
-  MI_TRY(dmalloc(&c->kv_pool, kv_elems, &c->kv_bytes));
-  MI_HIP(hipMemsetAsync(c->kv_pool, 0, kv_elems * 2, s));
+  MI_TRY(dmalloc(&c->kv_pool, kv_elems * c->kv_esz() / 2, &c->kv_bytes));
+  MI_HIP(hipMemsetAsync(c->kv_pool, 0, kv_elems * c->kv_esz(), s));   // e4m3: byte 0 is 0.0
+  if (c->kv_f8()) {
+    const int nb_seq = ceil_div(k.max_model_len, k.block_size);
+    MI_TRY(dmalloc(&c->kv_stage, kv_stage_elems(c), &c->workspace_bytes));
+    MI_TRY(dmalloc(&c->d_ident, (size_t)nb_seq, &c->workspace_bytes));
+    std::vector<int32_t> ident(nb_seq);
+    for (int i = 0; i < nb_seq; ++i) ident[i] = i;
+    MI_HIP(hipMemcpyAsync(c->d_ident, ident.data(), ident.size() * 4, hipMemcpyHostToDevice, s));
+    MI_HIP(hipStreamSynchronize(s));
+  }
   // RoPE tables (fp32 angles as HF computes them; llama3 rescale of the inverse frequencies)
   {
     const int half = c->hd / 2, P = k.max_model_len;
@@ -1414,8 +1470,8 @@ int mi_forward_spec(mi_ctx* t, mi_ctx* d, int32_t B, int32_t k, const int64_t* i
   const mi_model_config& kt = t0->cfg;
   const mi_model_config& kd = d->cfg;
   MI_CHECK(kt.device_id == kd.device_id && kt.block_size == kd.block_size && kt.num_blocks == kd.num_blocks &&
-           kt.vocab_size == kd.vocab_size && kt.max_model_len == kd.max_model_len,
-           "mi_forward_spec: target (rank 0) and draft must share device, block_size, num_blocks, vocab_size and max_model_len");
+           kt.vocab_size == kd.vocab_size && kt.max_model_len == kd.max_model_len && kt.kv_cache_dtype == kd.kv_cache_dtype,
+           "mi_forward_spec: target (rank 0) and draft must share device, block_size, num_blocks, vocab_size, max_model_len and kv_cache_dtype");
   MI_CHECK(B >= 1 && k >= 1 && B * k <= kt.max_num_seqs && B <= kd.max_num_seqs,
            "mi_forward_spec: B * k rows exceed the target's max_num_seqs (or B the draft's)");
   int n_catch = 0;
@@ -1826,6 +1882,34 @@ int mi_op_paged_attn_prefill(const void* q, int32_t T, int32_t q_pos0, const voi
   const uint16_t* vp = kp + (size_t)num_blocks * nkv * block_size * hd;
   return launch_attn_prefill(reinterpret_cast<const uint16_t*>(q), T, q_pos0, kp, vp, block_size, block_table, nh, nkv,
                              hd, reinterpret_cast<uint16_t*>(out), (hipStream_t)stream);
+}
+int mi_op_kv_write_f8(const void* k, const void* v, const int64_t* slots, int32_t T, int32_t nkv, int32_t hd, void* pool_u8,
+                      int32_t num_blocks, int32_t block_size, float k_scale, float v_scale, void* stream) {
+  MI_CHECK(k && v && slots && pool_u8, "null argument");
+  uint8_t* kp = reinterpret_cast<uint8_t*>(pool_u8);
+  uint8_t* vp = kp + (size_t)num_blocks * nkv * block_size * hd;
+  return launch_kv_write_f8(reinterpret_cast<const uint16_t*>(k), reinterpret_cast<const uint16_t*>(v), slots, T, nkv, hd,
+                            kp, vp, block_size, k_scale, v_scale, (hipStream_t)stream);
+}
+int mi_op_paged_attn_decode_f8(const void* q, const void* pool_u8, int32_t num_blocks, int32_t block_size,
+                               const int32_t* block_table, int32_t MB, const int32_t* ctx_lens, int32_t B, int32_t nh,
+                               int32_t nkv, int32_t hd, float k_scale, float v_scale, void* out, void* scratch,
+                               void* stream) {
+  MI_CHECK(q && pool_u8 && block_table && ctx_lens && out && scratch, "null argument");
+  MI_CHECK(num_blocks >= 1, "attention: empty pool");
+  const uint8_t* kp = reinterpret_cast<const uint8_t*>(pool_u8);
+  const uint8_t* vp = kp + (size_t)num_blocks * nkv * block_size * hd;
+  return launch_attn_decode_f8(reinterpret_cast<const uint16_t*>(q), kp, vp, block_size, block_table, MB, ctx_lens, B, nh,
+                               nkv, hd, k_scale, v_scale, reinterpret_cast<uint16_t*>(out), scratch, (hipStream_t)stream,
+                               /*rows_per_seq=*/1, num_blocks);   // the pool size is known: a wave's first K/V request goes out early
+}
+int mi_op_kv_dequant_gather(const void* pool_u8, int32_t num_blocks, int32_t block_size, const int32_t* block_table,
+                            int32_t MB, int32_t kv_len, int32_t nkv, int32_t hd, float k_scale, float v_scale,
+                            void* staged_bf16, void* stream) {
+  MI_CHECK(pool_u8 && block_table && staged_bf16, "null argument");
+  MI_CHECK(k_scale > 0.f && v_scale > 0.f, "kv_dequant_gather: FP8 KV scales must be positive");
+  return launch_kv_dequant_gather(reinterpret_cast<const uint8_t*>(pool_u8), num_blocks, block_size, block_table, MB, kv_len,
+                                  nkv, hd, k_scale, v_scale, reinterpret_cast<uint16_t*>(staged_bf16), (hipStream_t)stream);
 }
 
 }  // extern "C"

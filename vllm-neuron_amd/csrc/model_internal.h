@@ -54,9 +54,14 @@ struct mi_ctx {
   Linear lm_head;
   float* g_final = nullptr;
   bool have_lm_head = false;
-  // KV pool: [L][2][NB][nkv_l][bs][hd] bf16
+  // KV pool: [L][2][NB][nkv_l][bs][hd] bf16, or e4m3 bytes (cfg.kv_cache_dtype = MI_KV_F8E4M3)
   uint16_t* kv_pool = nullptr;
   size_t kv_half = 0;  // elements of one K (or V) pool of one layer
+  bool kv_f8() const { return cfg.kv_cache_dtype == MI_KV_F8E4M3; }
+  size_t kv_esz() const { return kv_f8() ? 1 : 2; }
+  std::vector<float> k_scale, v_scale;   // FP8 KV: per-layer static scales (default 1.0)
+  uint16_t* kv_stage = nullptr;          // FP8 KV: one sequence's K/V as bf16 for context encoding [2][MB_cap][nkv_l][bs][hd]
+  int32_t* d_ident = nullptr;            // ... and its identity block table
   float *rope_cos = nullptr, *rope_sin = nullptr;
   // weight-load staging
   void* stage_raw = nullptr;

@@ -37,14 +37,15 @@ class MI355XEngine:
     def __init__(self, hf_config, model: str = "", *, max_model_len=2048, max_num_seqs=4, block_size=32,
                  num_gpu_blocks_override=None, enable_prefix_caching=True, tensor_parallel_size=1,
                  dtype="bfloat16", override_mi355x_config: dict | None = None, seed=0, local_rank=0,
-                 enable_chunked_prefill=False, max_num_batched_tokens=None, speculative_config=None):
+                 enable_chunked_prefill=False, max_num_batched_tokens=None, speculative_config=None,
+                 kv_cache_dtype="auto"):
         if HAVE_VLLM:  # pragma: no cover
             raise RuntimeError("vLLM is installed: use vllm.LLM(...) — the plugin registers itself")
         cfg = SimpleVllmConfig(
             model_config=SimpleModelConfig(model=model, hf_config=hf_config, dtype=dtype,
                                            max_model_len=max_model_len, seed=seed),
             cache_config=SimpleCacheConfig(block_size=block_size, num_gpu_blocks_override=num_gpu_blocks_override,
-                                           enable_prefix_caching=enable_prefix_caching),
+                                           enable_prefix_caching=enable_prefix_caching, cache_dtype=kv_cache_dtype),
             parallel_config=SimpleParallelConfig(tensor_parallel_size=tensor_parallel_size),
             scheduler_config=SimpleSchedulerConfig(max_num_seqs=max_num_seqs, max_model_len=max_model_len,
                                                    chunked_prefill_enabled=bool(enable_chunked_prefill),

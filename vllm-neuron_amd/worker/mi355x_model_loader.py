@@ -283,7 +283,7 @@ class MI355XCausalLM(MI355XModelBase):
         tp_devices = list(kwargs.get("tp_device_ids") or [])
         if tp_degree > 1 and len(tp_devices) != tp_degree:
             raise RuntimeError(f"tp_degree {tp_degree} needs {tp_degree} device ids, got {tp_devices}")
-        from .._native import MI_TP_ALL_RANKS, MI_TP_TRANSPORT
+        from .._native import MI_KV, MI_TP_ALL_RANKS, MI_TP_TRANSPORT
         buckets = list(cfg.get("context_encoding_buckets") or [])
         max_num_seqs = int(cfg["batch_size"])
         chunked = cfg.get("chunked_prefill_config")
@@ -315,6 +315,7 @@ class MI355XCausalLM(MI355XModelBase):
             device_id=int(kwargs.get("device_id", 0)),
             use_graphs=int(cfg.get("use_graphs", 1)),
             prefill_fp8_activations=int(bool(cfg.get("prefill_fp8_activations", False))),
+            kv_cache_dtype=MI_KV[cfg.get("kv_cache_dtype", "auto")],
             **geo)
         if fused_spec:
             self._load_draft(speculative_config, cfg, num_blocks, block_size, max_num_seqs, max_model_len, buckets,
@@ -428,7 +429,8 @@ class MI355XCausalLM(MI355XModelBase):
             # the draft is not sharded: it runs on the GPU of the target's rank 0
             tp_degree=1, tp_rank=0, device_id=int((kwargs.get("tp_device_ids") or [kwargs.get("device_id", 0)])[0]),
             use_graphs=int(cfg.get("use_graphs", 1)),
-            prefill_fp8_activations=int(bool(cfg.get("prefill_fp8_activations", False))), **geo)
+            prefill_fp8_activations=int(bool(cfg.get("prefill_fp8_activations", False))),
+            kv_cache_dtype=self.model.cfg.kv_cache_dtype, **geo)   # the draft's pool takes the target's dtype
         synthetic, state_dict = cfg.get("draft_synthetic_weights"), cfg.get("draft_state_dict")
         if synthetic is not None:
             self.draft.init_synthetic_weights(int(synthetic.get("seed", 2)), float(synthetic.get("std", 0.02)))
@@ -647,7 +649,20 @@ def _handle_pa_num_blocks(cache_config, mi355x_config: dict, override_config: di
     return mi355x_config
 
 
+def resolve_kv_cache_dtype(cache_dtype, mi355x_config: dict) -> str:
+    """vLLM's cache_config.cache_dtype and the kv_cache_quant override key -> "bfloat16" or "fp8_e4m3" (OCP e4m3fn with
+    static per-layer k_scale / v_scale).  Anything else, "fp8_e5m2" included, is refused here, not served from a bf16 pool."""
+    cache_dtype = "auto" if cache_dtype is None else str(cache_dtype)
+    if cache_dtype in ("fp8", "fp8_e4m3"):
+        return "fp8_e4m3"
+    if cache_dtype not in ("auto", "bfloat16"):
+        raise ValueError(f"kv cache dtype {cache_dtype!r} is not supported on the MI355X plugin: use 'auto', 'bfloat16', "
+                         "'fp8' or 'fp8_e4m3'")
+    return "fp8_e4m3" if mi355x_config.get("kv_cache_quant") else "bfloat16"
+
+
 def _validate_mi355x_config(cache_config, scheduler_config, mi355x_config: dict) -> dict:
+    mi355x_config["kv_cache_dtype"] = resolve_kv_cache_dtype(getattr(cache_config, "cache_dtype", "auto"), mi355x_config)
     if cache_config.enable_prefix_caching:
         assert mi355x_config.get("is_prefix_caching", False)
         assert mi355x_config.get("is_block_kv_layout", False)

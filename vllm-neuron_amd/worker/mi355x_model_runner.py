@@ -168,7 +168,9 @@ class MI355XModelRunner:
     def get_kv_cache_spec(self) -> dict:
         return {"layer": FullAttentionSpec(block_size=self.block_size,
                                            num_kv_heads=self.model.num_key_value_heads,
-                                           head_size=self.model.head_dim, dtype=torch.bfloat16,
+                                           head_size=self.model.head_dim,
+                                           dtype=(torch.float8_e4m3fn if self.model.mi355x_config.get("kv_cache_dtype") == "fp8_e4m3"
+                                                  else torch.bfloat16),
                                            sliding_window=None)}
 
     def _get_last_token_position(self, state: CachedRequestState) -> int:
