@@ -101,7 +101,7 @@ enum { MI_KV_BF16 = 0, MI_KV_F8E4M3 = 1 };
 enum { MI_TP_TRANSPORT_P2P = 0, MI_TP_TRANSPORT_RCCL = 1 };
 
 const char* mi_last_error(void);
-int mi_version(void);   /* 5 = this header (+ kv_cache_dtype and the FP8-KV entry points mi_op_kv_write_f8, mi_op_paged_attn_decode_f8, mi_op_kv_dequant_gather); 4 lacked them (+ mi_tp_plan, mi_tp_info); 3 lacked those; 2 lacked tp_device_ids / tp_transport / MI_TP_ALL_RANKS; 1 lacked mi_forward_tokens, mi_op_sample, mi_tp_init_transport */
+int mi_version(void);   /* 6 = this header (+ mi_op_paged_attn_prefill_f8: context encoding reads the FP8 pool natively); 5 lacked it (+ kv_cache_dtype and the FP8-KV entry points mi_op_kv_write_f8, mi_op_paged_attn_decode_f8, mi_op_kv_dequant_gather); 4 lacked them (+ mi_tp_plan, mi_tp_info); 3 lacked those; 2 lacked tp_device_ids / tp_transport / MI_TP_ALL_RANKS; 1 lacked mi_forward_tokens, mi_op_sample, mi_tp_init_transport */
 
 int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out);
 int mi_ctx_destroy(mi_ctx* ctx);
@@ -364,7 +364,17 @@ int mi_op_paged_attn_decode_f8(const void* q, const void* pool_u8, int32_t num_b
                                const int32_t* ctx_lens, int32_t B, int32_t nh, int32_t nkv,
                                int32_t hd, float k_scale, float v_scale, void* out, void* scratch,
                                void* stream);
-/* Context encoding over an FP8 pool: stage ONE sequence's keys 0 .. kv_len - 1 as bf16.
+/* mi_op_paged_attn_prefill over the byte pool (ABI 6): K and V codes go from the pool to LDS by
+ * LDS-DMA, are widened to bf16 once per work-group into the tile image the bf16 kernel's MFMAs
+ * read, and no bf16 copy of the sequence exists in memory.  k_scale is folded into the score
+ * scale, v_scale applied once to the normalised output.  block_size must be a multiple of 16.
+ * A context with kv_cache_dtype = MI_KV_F8E4M3 runs it for context encoding when
+ * MI355X_ATTN_PREFILL_F8_NATIVE=1 is set; its default is the staged form below. */
+int mi_op_paged_attn_prefill_f8(const void* q, int32_t T, int32_t q_pos0, const void* pool_u8,
+                                int32_t num_blocks, int32_t block_size, const int32_t* block_table,
+                                int32_t MB, int32_t nh, int32_t nkv, int32_t hd, float k_scale,
+                                float v_scale, void* out, void* stream);
+/* The staged form of the same (a context's default): stage ONE sequence's keys 0 .. kv_len - 1 as bf16.
  * block_table [MB] int32; staged_bf16 [2][ceil(kv_len / block_size)][nkv][block_size][hd] bf16 in
  * block-table order, element bf16_rne(float(code) * scale).  mi_op_paged_attn_prefill then runs on
  * staged_bf16 with num_blocks = ceil(kv_len / block_size) and the identity block table. */

@@ -53,6 +53,13 @@ int launch_attn_decode_f8(const uint16_t* q, const uint8_t* kpool, const uint8_t
                           const int32_t* block_table, int MB, const int32_t* ctx_lens, int B, int nh, int nkv, int hd,
                           float k_scale, float v_scale, uint16_t* out, void* scratch, hipStream_t s, int rows_per_seq = 1,
                           int num_blocks = 0);
+// launch_attn_prefill over the byte pool, read natively (attn_prefill_f8_kernel: codes widened once per work-group in
+// LDS, no bf16 copy in memory).  The same shape checks, plus block_size % 16 == 0 and positive scales; k_scale rides in
+// the score scale, v_scale multiplies the normalised output once.  No byte of a block the table names for keys
+// 0 .. q_pos0 + T - 1 may be the e4m3 NaN code (masking is by score, as for launch_attn_decode_f8).
+int launch_attn_prefill_f8(const uint16_t* q, int T, int q_pos0, const uint8_t* kpool, const uint8_t* vpool,
+                           int block_size, const int32_t* block_table, int nh, int nkv, int hd, float k_scale,
+                           float v_scale, uint16_t* out, hipStream_t s);
 // One sequence's blocks 0 .. ceil(kv_len / block_size) - 1, in block-table order, widened to a bf16 pool
 // staged [2][nblk][nkv][block_size][hd] (element bf16_rne(float(code) * scale)) that launch_attn_prefill reads with an
 // identity block table.  pool: K bytes, then V bytes (num_blocks blocks each).

@@ -1318,6 +1318,368 @@ int launch_attn_prefill(const uint16_t* q, int T, int q_pos0, const uint16_t* kp
 }
 
 // =====================================================================================
+// context encoding over an FP8 (e4m3) pool
+// =====================================================================================
+// attn_prefill2_kernel's work split, MFMA maps, deferred-rescale softmax and epilogue (see there) over the byte pool;
+// what differs is how K and V reach the bf16 tile image the MFMAs read.  Codes are widened ONCE per work-group, in LDS:
+//   * a K/V row is HD BYTES, a 1 KiB LDS-DMA piece is 1024 / HD keys (8 / 16) of one block and one kv head: contiguous
+//     in the pool, so lane i fetches bytes 16 i .. 16 i + 15 of the piece and the DMA needs no swizzled source.  A 64-key
+//     tile is NP K pieces + NP V pieces (8 + 8 / 4 + 4); piece p = wave + NW i goes to wave `wave` (head_dim 128: K piece
+//     w and V piece w; head_dim 64: waves 0-3 a K piece, waves 4-7 a V piece).  Pieces land in a CODE RING of three
+//     stages (K part, V part: 2 x 64 x HD bytes each);
+//   * every wave widens the pieces it fetched itself: its own counted vmcnt (no barrier: the code ring is wave-private,
+//     a lane even reads back exactly the 16 bytes it fetched), one ds_read_b128, 8 v_cvt_scalef32_pk_bf16_fp8 (exact),
+//     two ds_write_b128 into the bf16 TILE IMAGE: rows of HD bf16 with kv_swz<HD> chunks, i.e. what attn_prefill2_kernel's
+//     DMA would have left there.  Lanes of neighbouring keys write their two chunks in opposite order, so a group of 16
+//     lanes covers 16 different 16-byte slots;
+//   * the image is double-buffered.  Iteration t requests tile t + 3, multiplies tile t from image[t & 1], widens tile
+//     t + 1 into image[(t + 1) & 1] (under the tail of its own MFMAs), drains its LDS writes and passes ONE raw barrier: image[(t + 1) & 1] is complete for iteration t + 1
+//     and nobody still reads image[t & 1] when iteration t + 1 overwrites it with tile t + 2.
+// LDS: 3 x 16 KiB + 2 x 32 KiB = 112 KiB at head_dim 128 (56 KiB at 64): one work-group per CU, as the bf16 kernel.
+// Numerics: the image holds float(code) exactly, every MFMA is bf16, k_scale rides in the score scale,
+// v_scale multiplies the normalised output once; q, P and the output are rounded where attn_prefill2_kernel rounds them.
+// The widening's LDS instructions are inline asm (hipcc would drain the DMAs in flight in front of a read that may alias
+// them) and sit at the end of the iteration; the window of hand-counted lgkmcnt between the first transposed V read and
+// the last P.V MFMA is fenced: s_waitcnt lgkmcnt(0) + sched_barrier(0) in front, sched_barrier(0) behind.
+// Masking is by score (P = 0): as for attn_decode_f8_kernel, no byte of a block the table names may be the e4m3 NaN code.
+template <int HD, int NW>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_prefill_f8_kernel(
+    const uint16_t* __restrict__ q, int T, int q_pos0, const uint8_t* __restrict__ kpool,
+    const uint8_t* __restrict__ vpool, int bs, int bs_shift, const int32_t* __restrict__ block_table, int nh, int nkv,
+    int G, int Gp, int nblk, uint16_t* __restrict__ out, float score_scale, float v_scale) {
+  constexpr int TK = 64;                       // keys per tile
+  constexpr int ROWB = HD * 2;                 // bytes per K/V row of the bf16 image
+  constexpr int KPP = 1024 / HD;               // keys per 1 KiB piece of codes (8 / 16)
+  constexpr int NP = TK / KPP;                 // pieces per K (or V) tile (8 / 4)
+  constexpr int CPC = HD / 16;                 // 16-byte code chunks per row
+  constexpr int PW = 2 * NP / NW;              // pieces per wave and tile (2 / 1) = DMA instructions per wave and tile
+  static_assert(2 * NP % NW == 0 && PW >= 1, "the K and V pieces of a tile must divide over the waves");
+  constexpr int CSTAGE = 2 * TK * HD;          // code ring stage: K part, V part
+  constexpr int NSTAGE = 3;
+  constexpr int KIMG = TK * ROWB;              // bf16 image of a K (or V) tile
+  constexpr int ISTAGE = 2 * KIMG;
+  constexpr int KSTEPS = HD / 16, DB = HD / 32;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char* const img = smem + NSTAGE * CSTAGE;
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kvh = blockIdx.y;
+  const int QB = NW / Gp;
+  const int hl = wave % Gp, slot = wave / Gp;
+  const int head = kvh * G + min(hl, G - 1);
+  const bool head_ok = hl < G;
+  const int kv_len = q_pos0 + T;
+  const int last_piece_key = ((kv_len - 1) / KPP) * KPP;
+  const int qq = lane & 31, h = lane >> 5;
+  const int npair = (nblk + 1) >> 1;
+
+  // ---- per-lane constants ------------------------------------------------------------------------
+  // widening: lane i of piece p holds codes 16 cc .. 16 cc + 15 (cc = i % CPC) of key KPP (p % NP) + i / CPC of the K
+  // (p < NP) or V tile = chunks 2 cc, 2 cc + 1 of that image row; `flip` lanes write the odd chunk first
+  const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
+  const int cc = lane % CPC;
+  unsigned waddr[PW][2], caddr[PW];            // LDS byte addresses: image (relative to its buffer), code ring (to its stage)
+  bool flip;
+  {
+    const int kip = lane / CPC;
+    flip = HD == 128 ? (kip & 1) : ((kip >> 1) & 1);
+#pragma unroll
+    for (int i = 0; i < PW; ++i) {
+      const int p = wave + NW * i, key = KPP * (p % NP) + kip;
+      const unsigned row = smem_lds + NSTAGE * CSTAGE + (p >= NP ? KIMG : 0) + key * ROWB;
+      waddr[i][0] = row + (((2 * cc + (flip ? 1 : 0)) ^ kv_swz<HD>(key)) * 16);
+      waddr[i][1] = row + (((2 * cc + (flip ? 0 : 1)) ^ kv_swz<HD>(key)) * 16);
+      caddr[i] = smem_lds + p * 1024 + lane * 16;
+    }
+  }
+  // K row reads (A operand of S^T): key qq of a 32-key block, chunk 2 ks + h
+  int kaddr[KSTEPS];
+#pragma unroll
+  for (int ks = 0; ks < KSTEPS; ++ks) kaddr[ks] = qq * ROWB + (((2 * ks + h) ^ kv_swz<HD>(qq)) * 16);
+  // V transposed reads (A operand of O^T): see attn_prefill2_kernel
+  const int gi = lane >> 4, qr = (lane & 15) >> 2, pc = lane & 3;
+  int vaddr[DB][2];
+#pragma unroll
+  for (int db = 0; db < DB; ++db)
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int key = 4 * h + qr + 8 * u;
+      const int chunk = 4 * db + 2 * (gi & 1) + (pc >> 1);
+      vaddr[db][u] = key * ROWB + ((chunk ^ kv_swz<HD>(key)) * 16) + 8 * (pc & 1);
+    }
+
+  const int passes = QB == 1 ? 2 : 1;
+  for (int pass = 0; pass < passes; ++pass) {
+    // ---- which query block this wave owns (attn_prefill2_kernel's complementary pairs) ---------------
+    int blk_q, pair;
+    bool blk_ok;
+    if (QB == 1) {
+      pair = blockIdx.x;
+      blk_q = pass == 0 ? nblk - 1 - pair : pair;
+      blk_ok = pair < npair && !(pass == 1 && pair == nblk - 1 - pair);
+    } else {
+      pair = (int)blockIdx.x * (QB >> 1) + (slot >> 1);
+      blk_q = (slot & 1) ? nblk - 1 - pair : pair;
+      blk_ok = pair < npair && !((slot & 1) && pair == nblk - 1 - pair);
+    }
+    const int q0 = blk_q * 32;
+    const bool active = blk_ok && head_ok;
+    const int p_first = q_pos0 + min(q0, T - 1), p_last = q_pos0 + min(q0 + 31, T - 1);
+    const int nt_wave = active ? p_last / TK + 1 : 0;
+    int wg_pair0 = QB == 1 ? (int)blockIdx.x : (int)blockIdx.x * (QB >> 1);
+    int wg_blk = QB == 1 ? (pass == 0 ? nblk - 1 - wg_pair0 : wg_pair0) : nblk - 1 - wg_pair0;   // heaviest block of the work-group
+    wg_blk = max(min(wg_blk, nblk - 1), 0);
+    const int nt = (q_pos0 + min(wg_blk * 32 + 31, T - 1)) / TK + 1;
+
+    // ---- Q fragments (B operand of S^T): Q[q0 + qq][16 ks + 8 h ..] ---------------------------------
+    const int qi = min(q0 + qq, T - 1);
+    const int qpos = q_pos0 + qi;
+    u32x4_t qf[KSTEPS];
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ++ks)
+      qf[ks] = active ? *reinterpret_cast<const u32x4_t*>(q + ((size_t)qi * nh + head) * HD + ks * 16 + h * 8) : u32x4_t{0, 0, 0, 0};
+
+    f32x16_t o[DB];
+#pragma unroll
+    for (int db = 0; db < DB; ++db)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+    float m_used = -INFINITY, lsum = 0.f;
+
+    // Block ids (scalar loads) are fetched one tile ahead of the DMAs that use them, as in attn_prefill2_kernel.
+    int pf_blk[PW], pf_off[PW];
+    auto fetch_ids = [&](int t) {
+#pragma unroll
+      for (int i = 0; i < PW; ++i) {
+        const int k0 = min(t * TK + ((wave + NW * i) % NP) * KPP, last_piece_key);   // past the context: the last piece again (masked by position)
+        int bi;
+        if (bs_shift >= 0) { bi = k0 >> bs_shift; pf_off[i] = k0 & (bs - 1); }
+        else { bi = k0 / bs; pf_off[i] = k0 - bi * bs; }
+        pf_blk[i] = block_table[bi];
+      }
+    };
+    auto issue = [&](int st) {                  // the tile whose ids fetch_ids loaded last
+#pragma unroll
+      for (int i = 0; i < PW; ++i) {
+        const int p = wave + NW * i;
+        const size_t row = ((size_t)pf_blk[i] * nkv + kvh) * bs + pf_off[i];
+        glds16((p >= NP ? vpool : kpool) + row * HD + lane * 16, smem + st * CSTAGE + p * 1024);
+      }
+    };
+    // tile u: wave-private code stage -> the work-group's image[u & 1].  Tiles u + 1 and u + 2 stay in flight.
+    int st_issue = 0, st_widen = 0;
+    auto widen = [&](int u) {
+      if (u + 2 < nt) {
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PW) : "memory");
+      } else if (u + 1 < nt) {
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PW) : "memory");
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      const unsigned coff = st_widen * CSTAGE, ioff = (u & 1) * ISTAGE;
+      st_widen = st_widen == NSTAGE - 1 ? 0 : st_widen + 1;
+      u32x4_t cw[PW];
+#pragma unroll
+      for (int i = 0; i < PW; ++i) asm volatile("ds_read_b128 %0, %1" : "=v"(cw[i]) : "v"(caddr[i] + coff) : "memory");
+      // (0, not counted: scalar loads share the counter and return out of order)
+      if constexpr (PW == 2) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cw[0]), "+v"(cw[PW - 1]) : : "memory");
+      else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cw[0]) : : "memory");
+#pragma unroll
+      for (int i = 0; i < PW; ++i) {
+        const bf16x8_t lo = decode8<MI_W_F8E4M3>(cw[i][0], cw[i][1]), hi = decode8<MI_W_F8E4M3>(cw[i][2], cw[i][3]);
+        asm volatile("ds_write_b128 %0, %1" ::"v"(waddr[i][0] + ioff), "v"(flip ? hi : lo) : "memory");
+        asm volatile("ds_write_b128 %0, %1" ::"v"(waddr[i][1] + ioff), "v"(flip ? lo : hi) : "memory");
+      }
+    };
+
+    fetch_ids(0);
+    issue(0);
+    if (nt > 1) { fetch_ids(1); issue(1); }
+    if (nt > 2) { fetch_ids(2); issue(2); }
+    fetch_ids(3);                              // st_issue: 3 % NSTAGE = 0
+    // (the Q fragments' wait in front of the loop, not as a vmcnt(0) inside it: see attn_prefill2_kernel)
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ++ks) asm volatile("" : "+v"(qf[ks]));
+    widen(0);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();              // image[0] holds tile 0 (and the previous pass is done with both images)
+    for (int t = 0; t < nt; ++t) {
+      if (t + 3 < nt) {                          // into the stage tile t left when it was widened; ids one tile ahead
+        issue(st_issue);
+        st_issue = st_issue == NSTAGE - 1 ? 0 : st_issue + 1;
+        fetch_ids(t + 4);
+      }
+      const unsigned char* Kst = img + (t & 1) * ISTAGE;
+      const unsigned char* Vst = Kst + KIMG;
+      if (t < nt_wave) {                         // wave-uniform: else the tile lies in this block's future (or the slot is idle)
+      // ---- S^T = K . Q^T : two 32-key blocks, K fragments requested one block ahead of their MFMAs ----
+      f32x16_t sc[2];
+      {
+        bf16x8_t kf[KSTEPS];
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks) kf[ks] = *reinterpret_cast<const bf16x8_t*>(Kst + kaddr[ks]);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) sc[b][r] = 0.f;
+#pragma unroll
+          for (int ks = 0; ks < KSTEPS; ++ks) {
+            sc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], __builtin_bit_cast(bf16x8_t, qf[ks]), sc[b], 0, 0, 0);
+            if (b == 0) kf[ks] = *reinterpret_cast<const bf16x8_t*>(Kst + 32 * ROWB + kaddr[ks]);
+          }
+        }
+        __builtin_amdgcn_sched_group_barrier(0x100, KSTEPS, 0);
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks) {
+          __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks) __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+      }
+      // ---- online softmax: this lane holds 32 scores of query qq (keys (r & 3) + 8 (r >> 2) + 4 h of each block) ----
+      const bool need_mask = t * TK + TK - 1 > p_first;
+      if (need_mask) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (t * TK + 32 * b + (r & 3) + 8 * (r >> 2) + 4 * h > qpos) sc[b][r] = -INFINITY;
+      }
+      float mx = sc[0][0];
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sc[b][r]);
+      {
+        const f32x2_t sw = swap32_pair(mx);
+        mx = fmaxf(sw[0], sw[1]);
+      }
+      const float ms = mx * score_scale;         // key 0 is visible to every query: finite from the first tile on
+      const bool moved = ms > m_used + kDeferLog2;
+      if (__any(moved)) {
+        const float mn = moved ? ms : m_used;
+        const float alpha = moved ? fexp2(m_used - mn) : 1.f;   // exp2(-inf) = 0 on the first tile
+        m_used = mn;
+        lsum *= alpha;
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
+      }
+      // ---- p = exp2(s - m) packed to bf16 = the B operands of O^T += V^T . P^T; transposed V fragments by inline asm,
+      // kVAhead MFMAs ahead of their use, completion counted by hand inside the fenced window ----
+      constexpr int NPV = 4 * DB;               // MFMAs: (b, s2) outer, d-block inner
+      constexpr int kVAhead = 4;
+      s16x4_t vlo[NPV], vhi[NPV];
+      unsigned vbase[DB][2];
+      const unsigned vst_lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)Vst;
+#pragma unroll
+      for (int db = 0; db < DB; ++db) { vbase[db][0] = vst_lds + vaddr[db][0]; vbase[db][1] = vst_lds + vaddr[db][1]; }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the widening's writes, the block ids, the K fragments: nothing outstanding
+      __builtin_amdgcn_sched_barrier(0);                   // ... and nothing moves into the window
+#define MI_VREAD(i_)                                                                                                         \
+      do {                                                                                                                   \
+        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(vlo[i_]) : "v"(vbase[(i_) % DB][0]), "n"(16 * ((i_) / DB) * ROWB)); \
+        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(vhi[i_]) : "v"(vbase[(i_) % DB][1]), "n"(16 * ((i_) / DB) * ROWB)); \
+      } while (0)
+      MI_VREAD(0); MI_VREAD(1); MI_VREAD(2); MI_VREAD(3);
+      static_assert(kVAhead == 4, "the prefetch above is written out for 4");
+      bf16x8_t pb[4];
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        float pv[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          pv[r] = fexp2(fmaf(sc[b][r], score_scale, -m_used));   // masked: exp2(-inf) = 0
+          lsum += pv[r];
+        }
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          union { uint32_t w[4]; bf16x8_t v; } pk;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) pk.w[k] = pack_bf16x2(pv[8 * s2 + 2 * k], pv[8 * s2 + 2 * k + 1]);
+          pb[2 * b + s2] = pk.v;
+        }
+      }
+#define MI_PV(i_)                                                                                                            \
+      do {                                                                                                                   \
+        constexpr int issued = 2 * ((i_) + kVAhead < NPV ? (i_) + kVAhead : NPV);                                            \
+        asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(vlo[i_]), "+v"(vhi[i_]) : "n"(issued - 2 * ((i_) + 1)));               \
+        const s16x4_t lo = vlo[i_], hi = vhi[i_];                                                                            \
+        const bf16x8_t a = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};                                         \
+        o[(i_) % DB] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, pb[(i_) / DB], o[(i_) % DB], 0, 0, 0);                     \
+        if constexpr ((i_) + kVAhead < NPV) MI_VREAD((i_) + kVAhead);                                                        \
+      } while (0)
+      MI_PV(0); MI_PV(1); MI_PV(2); MI_PV(3); MI_PV(4); MI_PV(5); MI_PV(6); MI_PV(7);
+      if constexpr (NPV == 16) { MI_PV(8); MI_PV(9); MI_PV(10); MI_PV(11); MI_PV(12); MI_PV(13); MI_PV(14); MI_PV(15); }
+#undef MI_PV
+#undef MI_VREAD
+      __builtin_amdgcn_sched_barrier(0);
+      }
+      if (t + 1 < nt) widen(t + 1);              // under the tail of this tile's P.V MFMAs
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's share of image[(t + 1) & 1] is written
+      __builtin_amdgcn_s_barrier();            // tile t + 1 is whole; everyone is done reading tile t
+    }
+    // ---- epilogue: (O^T[d][q] / l) v_scale -> out[q][head][d], 16-byte stores by one v_permlane32_swap per pair of groups
+    {
+      const f32x2_t sw = swap32_pair(lsum);
+      lsum = sw[0] + sw[1];
+    }
+    const float inv = lsum > 0.f ? 1.f / lsum : 0.f;
+    const bool st_ok = active && q0 + qq < T;
+    uint16_t* orow = out + ((size_t)(q0 + qq) * nh + head) * HD;
+    auto fin = [&](float x) { return x * inv * v_scale; };
+#pragma unroll
+    for (int db = 0; db < DB; ++db)
+#pragma unroll
+      for (int k2 = 0; k2 < 4; k2 += 2) {      // dim groups k2, k2 + 1: dims 32 db + 8 k + 4 h + (0..3)
+        uint32_t a0 = pack_bf16x2(fin(o[db][4 * k2 + 0]), fin(o[db][4 * k2 + 1]));
+        uint32_t a1 = pack_bf16x2(fin(o[db][4 * k2 + 2]), fin(o[db][4 * k2 + 3]));
+        uint32_t b0 = pack_bf16x2(fin(o[db][4 * k2 + 4]), fin(o[db][4 * k2 + 5]));
+        uint32_t b1 = pack_bf16x2(fin(o[db][4 * k2 + 6]), fin(o[db][4 * k2 + 7]));
+        const auto x = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+        const auto y = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+        const u32x4_t v = {x[0], y[0], x[1], y[1]};
+        if (st_ok) *reinterpret_cast<u32x4_t*>(orow + 32 * db + 8 * (k2 + h)) = v;
+      }
+    // (no barrier here: the loop's last one covers the images, and the code ring is wave-private)
+  }
+}
+
+int launch_attn_prefill_f8(const uint16_t* q, int T, int q_pos0, const uint8_t* kpool, const uint8_t* vpool,
+                           int block_size, const int32_t* block_table, int nh, int nkv, int hd, float k_scale,
+                           float v_scale, uint16_t* out, hipStream_t s) {
+  MI_CHECK(hd == 64 || hd == 128, "attention: head_dim must be 64 or 128");
+  MI_CHECK(T >= 1 && q_pos0 >= 0, "attention: bad T / q_pos0");
+  MI_CHECK(nh % nkv == 0 && nh / nkv <= 8, "attention: q heads per kv head must be 1..8");
+  MI_CHECK(block_size >= 16 && block_size % 16 == 0, "attention: block_size must be a multiple of 16");   // a DMA piece (8 / 16 keys) never straddles blocks
+  MI_CHECK(ceil_div(q_pos0 + T, block_size) <= kPrefillMaxBlocks, "attention: context spans more than 4096 blocks");
+  MI_CHECK(k_scale > 0.f && v_scale > 0.f, "attention: the FP8 KV scales must be positive");
+  const int G = nh / nkv;
+  const int Gp = G <= 1 ? 1 : (G <= 2 ? 2 : (G <= 4 ? 4 : 8));
+  const float score_scale = 1.4426950408889634f / sqrtf((float)hd) * k_scale;
+  const int nblk = ceil_div(T, 32), npair = (nblk + 1) / 2, qb = 8 / Gp;
+  int bs_shift = -1;
+  for (int sh = 4; sh < 20; ++sh) if ((1 << sh) == block_size) bs_shift = sh;
+  const dim3 grid(ceil_div(npair, qb >= 2 ? qb / 2 : 1), nkv);
+  if (hd == 128) {
+    constexpr int lds = 3 * 2 * 64 * 128 + 2 * 2 * 64 * 256;
+    MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_prefill_f8_kernel<128, 8>), lds));
+    hipLaunchKernelGGL((attn_prefill_f8_kernel<128, 8>), grid, dim3(512), lds, s, q, T, q_pos0, kpool, vpool, block_size, bs_shift,
+                       block_table, nh, nkv, G, Gp, nblk, out, score_scale, v_scale);
+  } else {
+    constexpr int lds = 3 * 2 * 64 * 64 + 2 * 2 * 64 * 128;
+    MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_prefill_f8_kernel<64, 8>), lds));
+    hipLaunchKernelGGL((attn_prefill_f8_kernel<64, 8>), grid, dim3(512), lds, s, q, T, q_pos0, kpool, vpool, block_size, bs_shift,
+                       block_table, nh, nkv, G, Gp, nblk, out, score_scale, v_scale);
+  }
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+// =====================================================================================
 // standalone KV write (the model path writes K/V from the QKV epilogue instead)
 // =====================================================================================
 __global__ void kv_write_kernel(const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,

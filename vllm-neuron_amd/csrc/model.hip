@@ -234,6 +234,13 @@ static bool attn_early_kv() {   // MI355X_ATTN_EARLY_KV=0: the first K/V request
   return on;
 }
 
+// MI355X_ATTN_PREFILL_F8_NATIVE=1: FP8-KV context encoding by attn_prefill_f8_kernel on the byte pool instead of the bf16
+// staging pass (A/B; the staged path is the default because the native kernel is slower on a late chunk: DESIGN 5)
+static bool attn_prefill_f8_native() {
+  static const bool on = [] { const char* v = getenv("MI355X_ATTN_PREFILL_F8_NATIVE"); return v && v[0] == '1'; }();
+  return on;
+}
+
 int run_layers(mi_ctx* c, int rows, bool decode, int B, int MB, int q_pos0, int logits_rows,
                int logits_row0, const Seg* segs = nullptr, int nseg = 0) {
   const mi_model_config& k = c->cfg;
@@ -252,8 +259,11 @@ int run_layers(mi_ctx* c, int rows, bool decode, int B, int MB, int q_pos0, int 
     uint16_t* vpool = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(kpool) + c->kv_half * c->kv_esz());
     const uint8_t *kpool8 = reinterpret_cast<const uint8_t*>(kpool), *vpool8 = reinterpret_cast<const uint8_t*>(vpool);
     const float ksc = c->k_scale[l], vsc = c->v_scale[l];
-    // FP8 KV, context encoding: stage the sequence's keys 0 .. kv_len - 1 as bf16, then the bf16 kernel with the identity table
+    // FP8 KV, context encoding: stage the sequence's keys 0 .. kv_len - 1 as bf16, then the bf16 kernel with the identity
+    // table; the A/B switch runs the native kernel on the byte pool with the request's own table row instead
     auto prefill_f8 = [&](const uint16_t* qp, int n, int pos0, const int32_t* bt, uint16_t* outp) -> int {
+      if (attn_prefill_f8_native())
+        return launch_attn_prefill_f8(qp, n, pos0, kpool8, vpool8, k.block_size, bt, c->nh_l, c->nkv_l, c->hd, ksc, vsc, outp, s);
       const int nblk = ceil_div(pos0 + n, k.block_size);
       MI_TRY(launch_kv_dequant_gather(kpool8, k.num_blocks, k.block_size, bt, MB, pos0 + n, c->nkv_l, c->hd, ksc, vsc, c->kv_stage, s));
       return launch_attn_prefill(qp, n, pos0, c->kv_stage, c->kv_stage + (size_t)nblk * c->nkv_l * k.block_size * c->hd,
@@ -601,7 +611,7 @@ int capture_or_launch_decode(mi_ctx* c, int B, int MB) {
 extern "C" {
 
 const char* mi_last_error(void) { return mi::g_err.c_str(); }
-int mi_version(void) { return 5; }   // 5: + kv_cache_dtype, mi_op_kv_write_f8 / mi_op_paged_attn_decode_f8 / mi_op_kv_dequant_gather; 4: + mi_tp_plan, mi_tp_info; 3: + in-process tensor parallelism (tp_rank = MI_TP_ALL_RANKS, tp_device_ids, tp_transport)
+int mi_version(void) { return 6; }   // 6: + mi_op_paged_attn_prefill_f8; 5: + kv_cache_dtype, mi_op_kv_write_f8 / mi_op_paged_attn_decode_f8 / mi_op_kv_dequant_gather; 4: + mi_tp_plan, mi_tp_info; 3: + in-process tensor parallelism (tp_rank = MI_TP_ALL_RANKS, tp_device_ids, tp_transport)
 
 int mi_tp_plan(const mi_model_config* cfg, int32_t rank, mi_tp_plan_t* out) {
   MI_CHECK(cfg && out, "null argument");
@@ -1902,6 +1912,17 @@ int mi_op_paged_attn_decode_f8(const void* q, const void* pool_u8, int32_t num_b
   return launch_attn_decode_f8(reinterpret_cast<const uint16_t*>(q), kp, vp, block_size, block_table, MB, ctx_lens, B, nh,
                                nkv, hd, k_scale, v_scale, reinterpret_cast<uint16_t*>(out), scratch, (hipStream_t)stream,
                                /*rows_per_seq=*/1, num_blocks);   // the pool size is known: a wave's first K/V request goes out early
+}
+int mi_op_paged_attn_prefill_f8(const void* q, int32_t T, int32_t q_pos0, const void* pool_u8, int32_t num_blocks,
+                                int32_t block_size, const int32_t* block_table, int32_t MB, int32_t nh, int32_t nkv,
+                                int32_t hd, float k_scale, float v_scale, void* out, void* stream) {
+  MI_CHECK(q && pool_u8 && block_table && out, "null argument");
+  MI_CHECK(num_blocks >= 1 && block_size >= 1, "attention: empty pool");
+  MI_CHECK(ceil_div(q_pos0 + T, block_size) <= MB, "block_table narrower than the context");
+  const uint8_t* kp = reinterpret_cast<const uint8_t*>(pool_u8);
+  const uint8_t* vp = kp + (size_t)num_blocks * nkv * block_size * hd;
+  return launch_attn_prefill_f8(reinterpret_cast<const uint16_t*>(q), T, q_pos0, kp, vp, block_size, block_table, nh, nkv,
+                                hd, k_scale, v_scale, reinterpret_cast<uint16_t*>(out), (hipStream_t)stream);
 }
 int mi_op_kv_dequant_gather(const void* pool_u8, int32_t num_blocks, int32_t block_size, const int32_t* block_table,
                             int32_t MB, int32_t kv_len, int32_t nkv, int32_t hd, float k_scale, float v_scale,
