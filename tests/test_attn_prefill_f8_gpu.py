@@ -53,6 +53,33 @@ def test_paged_attn_prefill_f8(lib, hd, nh, nkv, T, pos0, bs, ks, vs):
     assert err < 0.03, err     # the project's bar for this op (P is rounded to bf16; the widening adds no error term)
 
 
+# G 4 with two blocks per work-group; Gp 8 with an idle head slot and two passes; G 1
+@pytest.mark.parametrize("hd,nh,nkv", [(128, 8, 2), (64, 7, 1), (128, 2, 2)])
+# tile and block edges plus a prefix; a block size that is no power of two; more tiles than ring stages
+@pytest.mark.parametrize("T,pos0,bs", [(65, 63, 32), (130, 96, 48), (300, 0, 32)])
+@pytest.mark.parametrize("ks,vs", [(1.0, 1.0), (0.25, 0.5)])
+def test_prefill_f8_native_equals_staged_bits(lib, hd, nh, nkv, T, pos0, bs, ks, vs):
+    """At power-of-two scales the native kernel and the staged path (mi_op_kv_dequant_gather, then mi_op_paged_attn_prefill
+    on the staged copy with an identity table) give the same bits: the two kernels run the same S^T / softmax / P.V step, and scaling every
+    K, and separately every V, by a power of two commutes exactly with each fp32 operation and bf16 rounding on the path
+    (no value here is near the denormal range)."""
+    kv_len = pos0 + T
+    nblk = (kv_len + bs - 1) // bs
+    nb, bt = scattered_table(kv_len, bs, 8)
+    pool, _, _ = code_pool(nb, bs, nkv, hd, 7, ks, vs)
+    q = torch.randn(T, nh, hd, generator=torch.Generator().manual_seed(9)).to(torch.bfloat16)
+    native = run_op(lib, q, T, pos0, pool, nb, bs, bt, nh, nkv, hd, ks, vs).to(torch.bfloat16)
+    staged = torch.empty(2, nblk, nkv, bs, hd, dtype=torch.bfloat16, device="cuda")
+    out = torch.empty(T, nh * hd, dtype=torch.bfloat16, device="cuda")
+    qd, btd, ident = q.cuda(), bt.cuda(), torch.arange(nblk, dtype=torch.int32).cuda()
+    lib.check(lib.load_library().mi_op_kv_dequant_gather(pool.data_ptr(), nb, bs, btd.data_ptr(), bt.numel(), kv_len, nkv,
+                                                         hd, ks, vs, staged.data_ptr(), None))
+    lib.check(lib.load_library().mi_op_paged_attn_prefill(qd.data_ptr(), T, pos0, staged.data_ptr(), nblk, bs,
+                                                          ident.data_ptr(), nblk, nh, nkv, hd, out.data_ptr(), None))
+    torch.cuda.synchronize()
+    assert torch.equal(native, out.cpu())
+
+
 def test_paged_attn_prefill_f8_rescale_branch(lib):
     """A spiked key late in the context (6 x the query of row T - 3, head 1; codes ~100, far below 448): the deferred
     rescale of the running maximum must fire, with k_scale inside the score scale that decides it."""

@@ -1,5 +1,5 @@
 """Dev tool: context-encoding attention alone (mi_op_paged_attn_prefill) at the Llama-3.1-8B head geometry, per bucket.
-    python tools/attn_prefill_time.py            (MI355X_ATTN_PREFILL_V1=1 for the first-generation kernel)"""
+    python tools/attn_prefill_time.py [T:pos0 ...]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -30,4 +30,4 @@ for T, pos0 in cases:
     b.record(); torch.cuda.synchronize()
     us = a.elapsed_time(b) * 1e3 / reps
     fl = 4 * nh * hd * (T * T / 2 + T * pos0)
-    print(f"T={T} pos0={pos0}: {us:.1f} us  {fl / us / 1e9:.3f} PF/s  (v1={os.environ.get('MI355X_ATTN_PREFILL_V1', '0')})", flush=True)
+    print(f"T={T} pos0={pos0}: {us:.1f} us  {fl / us / 1e9:.3f} PF/s", flush=True)

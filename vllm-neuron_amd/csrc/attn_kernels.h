@@ -32,7 +32,8 @@ int launch_attn_decode(const uint16_t* q, const uint16_t* kpool, const uint16_t*
 // only ever touched by these launches (which leave them at zero): enables the in-launch merge
 
 // One sequence: q [T, nh, hd] at absolute positions q_pos0.., keys 0..q_pos0+T-1 from the pool.
-// The sequence's block table is staged in LDS once: at most kPrefillMaxBlocks blocks (131072 tokens at block_size 32).
+// A sequence may span at most kPrefillMaxBlocks blocks (131072 tokens at block_size 32): the bound mi_ctx_create holds
+// max_model_len to, so every context that exists fits; the kernels themselves read the block table from memory.
 constexpr int kPrefillMaxBlocks = 4096;
 int launch_attn_prefill(const uint16_t* q, int T, int q_pos0, const uint16_t* kpool,
                         const uint16_t* vpool, int block_size, const int32_t* block_table, int nh,

@@ -10,9 +10,19 @@
 // merged by attn_combine_kernel in a fixed order (deterministic); otherwise one work-group
 // covers the whole sequence.
 //
-// Context encoding (attn_prefill_kernel): MFMA flash attention over the same pool.  Scores
-// are computed transposed (S^T = K.Q^T) so the accumulator registers ARE the B operand of
-// the P.V product (no LDS round trip for P); V is staged transposed in LDS.
+// attn_decode_f8_kernel is the same walk over an FP8 (e4m3) pool: 64-token tiles of bytes, codes widened to bf16 in
+// registers.
+//
+// Context encoding (attn_prefill2_kernel over a bf16 pool, attn_prefill_f8_kernel over an FP8 pool): MFMA flash
+// attention, one wave per 32-query block of one q head, the waves of a kv group sharing 64-key K/V tiles that LDS-DMA
+// brings into a ring in LDS.  Scores are computed transposed (S^T = K.Q^T) so the accumulator registers ARE the B
+// operand of the P.V product (no LDS round trip for P); V stays row-major in LDS and is read transposed.  The two
+// kernels have the same maps, query-block ownership, S^T / softmax / P.V step and epilogue and differ in how a tile
+// reaches its bf16 image in LDS: straight by DMA, or as codes that the work-group widens once.
+//
+// Also here: the standalone K/V writes into either pool and the FP8 -> bf16 staging gather.
+
+#include <type_traits>
 
 #include "attn_kernels.h"
 
@@ -698,260 +708,9 @@ int launch_attn_decode_f8(const uint16_t* q, const uint8_t* kpool, const uint8_t
 }
 
 // =====================================================================================
-// context encoding
+// context encoding: 32x32x16 MFMAs, K/V tiles by LDS-DMA, two waves per SIMD
 // =====================================================================================
-// One work-group per (32*QB queries, kv head): wave w owns q head (w % Gp) of the kv group and
-// query block (w / Gp), i.e. 32 queries = two 16-query MFMA tiles that share every K / V
-// fragment; the G heads of the group share the K/V tiles staged in LDS (one HBM read per group).
-// Per 64-key tile:  S^T_u[key][q] = K_u . Q^T        (u = 0..3: four 16-key MFMA tiles)
-//                   O^T[d][q]    += V^T[d][key] . P^T[key][q]   (two k-steps of 32 keys)
-// The MFMA k-slot (g, j) of P.V k-step kk is bound to key 32 kk + (j < 4 ? 4g + j : 16 + 4g + j - 4),
-// which is where S^T_{2kk} / S^T_{2kk+1} already hold that key's score for lane (g, q): the
-// exponentiated accumulators are the B operand as they stand (no LDS round trip for P).  V stays
-// row-major in LDS; its transposed A fragments come from ds_read_b64_tr_b16 (4 keys x 16 dims
-// per 16-lane group).  Next tile's K/V are prefetched into registers under the MFMAs.
-
-template <int HD, int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void attn_prefill_kernel(
-    const uint16_t* __restrict__ q, int T, int q_pos0, const uint16_t* __restrict__ kpool,
-    const uint16_t* __restrict__ vpool, int bs, const int32_t* __restrict__ block_table, int nh, int nkv, int G,
-    int Gp, int paired, uint16_t* __restrict__ out, float scale_log2e) {
-  // row pitch (elements): head_dim + 16, i.e. 288 B = 72 banks (head_dim 128) or 160 B = 40 banks (64).  Either way the 16 rows
-  // of a ds_read_b128 lane group start on 16 different 4-bank windows (its lanes of the next 16-byte column take the windows in
-  // between) and the 8 rows of a ds_read_b64_tr_b16 group own 8 banks each: no conflicts.  (At head_dim + 8 one pair of lanes
-  // per group met on a bank: 37 % of the LDS cycles, SQ_LDS_BANK_CONFLICT.)
-  constexpr int KP = HD + 16;
-  constexpr int CPR = HD / 8;   // 16-byte chunks per row
-  constexpr int DN = HD / 16, KS = HD / 32;
-  constexpr int TK = 64;        // keys per tile
-  constexpr int LD = (TK * CPR) / (WAVES * 64);  // 16-byte loads per thread per K (or V) tile
-  __shared__ __attribute__((aligned(16))) uint16_t Ks[TK * KP];
-  __shared__ __attribute__((aligned(16))) uint16_t Vs[TK * KP];
-  __shared__ int32_t bt_lds[kPrefillMaxBlocks];   // this sequence's block table: one L2 trip, not one per tile
-
-  constexpr int nthr = WAVES * 64, waves = WAVES;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int g = lane >> 4, c = lane & 15;
-  const int kvh = blockIdx.y, QB = waves / Gp;
-  const int hl = wave % Gp, qb = wave / Gp;
-  const bool head_ok = hl < G;
-  const int head = kvh * G + min(hl, G - 1);
-  const int kv_len = q_pos0 + T;
-  for (int i = threadIdx.x; i < ceil_div(kv_len, bs); i += nthr) bt_lds[i] = block_table[i];
-
-  // Causal work grows linearly with the query block index.  paired (long prompts): a work-group
-  // takes block x and then its complement (nblk - 1 - x), every work-group the same number of key
-  // tiles, one work-group per CU.  Otherwise one block per work-group, heaviest first: two
-  // work-groups share a CU (a wave's softmax arithmetic runs under the other's MFMAs) and the
-  // dispatcher hands out the light blocks as the heavy ones finish.  (Measured on Llama-8B shapes:
-  // unpaired wins 1-3 % of the whole prefill up to the 1024 bucket, pairing wins 9 % at 2048.)
-  const int nblk = ceil_div(T, 32 * QB);
-  for (int pass = 0; pass < (paired ? 2 : 1); ++pass) {
-  const int xb = !paired ? nblk - 1 - (int)blockIdx.x : (pass == 0 ? (int)blockIdx.x : nblk - 1 - (int)blockIdx.x);
-  if (pass == 1 && xb <= (int)blockIdx.x) break;   // odd count: the middle block is done once
-  const int wg_q0 = xb * 32 * QB;
-  const int q0 = wg_q0 + 32 * qb;            // this wave's 32 queries
-
-  u32x4_t qf[2][KS];
-  int qpos[2];
-  bool qok[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int qi = q0 + 16 * t + c;
-    qok[t] = head_ok && qi < T;
-    qpos[t] = q_pos0 + min(qi, T - 1);
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-      qf[t][ks] = qok[t] ? *reinterpret_cast<const u32x4_t*>(q + ((size_t)qi * nh + head) * HD + ks * 32 + g * 8)
-                         : u32x4_t{0, 0, 0, 0};
-  }
-  f32x4_t acc[2][DN];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int dn = 0; dn < DN; ++dn) acc[t][dn] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  float mrow[2] = {-INFINITY, -INFINITY}, lrow[2] = {0.f, 0.f};
-
-  const int wg_last_pos = q_pos0 + min(wg_q0 + 32 * QB - 1, T - 1);
-  const int ntiles = wg_last_pos / TK + 1;
-  const int w_first_pos = q_pos0 + min(q0, T - 1), w_last_pos = q_pos0 + min(q0 + 31, T - 1);
-
-  __syncthreads();   // block table staged (pass 0) / previous pass done with the K/V tiles
-  // register prefetch of one K/V tile (each thread: LD chunks of K and of V)
-  // Two register sets, two tiles ahead: with one wave per SIMD a tile's arithmetic (~1 us) is
-  // shorter than an HBM round trip, so the tile after next is requested before this one is used.
-  // (ext vectors: hipcc keeps arrays of them in VGPRs; HIP's uint4 struct goes to scratch)
-  u32x4_t kregA[LD], vregA[LD], kregB[LD], vregB[LD];
-  auto prefetch = [&](u32x4_t (&kreg)[LD], u32x4_t (&vreg)[LD], int tile) {
-    tile = min(tile, ntiles - 1);
-#pragma unroll
-    for (int i = 0; i < LD; ++i) {
-      const int idx = tid + i * nthr;
-      const int key = idx / CPR, ch = idx % CPR;
-      const int ta = min(tile * TK + key, kv_len - 1);   // clamp: rows past the context are masked anyway
-      const int blk = bt_lds[ta / bs];
-      const size_t src = (((size_t)blk * nkv + kvh) * bs + (ta % bs)) * HD + ch * 8;
-      kreg[i] = *reinterpret_cast<const u32x4_t*>(kpool + src);
-      vreg[i] = *reinterpret_cast<const u32x4_t*>(vpool + src);
-    }
-  };
-  prefetch(kregA, vregA, 0);
-  prefetch(kregB, vregB, 1);
-
-  auto do_tile = [&](u32x4_t (&kreg)[LD], u32x4_t (&vreg)[LD], int tile) {
-    __syncthreads();  // every wave is done reading the previous tile
-#pragma unroll
-    for (int i = 0; i < LD; ++i) {
-      const int idx = tid + i * nthr;
-      const int key = idx / CPR, ch = idx % CPR;
-      *reinterpret_cast<u32x4_t*>(&Ks[key * KP + ch * 8]) = kreg[i];
-      *reinterpret_cast<u32x4_t*>(&Vs[key * KP + ch * 8]) = vreg[i];
-    }
-    __syncthreads();
-    prefetch(kreg, vreg, tile + 2);
-    if (tile * TK > w_last_pos) return;   // wave-uniform: every key of this tile is in this wave's future
-
-    // ---- S^T = K . Q^T ------------------------------------------------------------------
-    // One wave per SIMD: latency is hidden by issue order, not by other waves.  All 16 K
-    // fragments are requested first, then the 32 MFMAs run back to back.
-    bf16x8_t kf[4][KS];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks)
-        kf[u][ks] = *reinterpret_cast<const bf16x8_t*>(&Ks[(16 * u + c) * KP + ks * 32 + g * 8]);
-    f32x4_t st[4][2];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      st[u][0] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-      st[u][1] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        st[u][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[u][ks], __builtin_bit_cast(bf16x8_t, qf[0][ks]), st[u][0], 0, 0, 0);
-        st[u][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[u][ks], __builtin_bit_cast(bf16x8_t, qf[1][ks]), st[u][1], 0, 0, 0);
-      }
-    }
-    // V^T fragments for the P.V product: requested now, so their LDS latency runs under the
-    // softmax arithmetic.  tr read: lane 4q' + p of a 16-lane group addresses row q' (a key),
-    // columns 4p..4p+3 (dims); lane i receives column i (dim 16 dn + i) of the 4 rows = 4
-    // consecutive k-slots of the A fragment.
-    const int tr_row = (lane & 15) >> 2, tr_col = (lane & 3) * 4;
-    s16x4_t vlo[2][DN], vhi[2][DN];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int dn = 0; dn < DN; ++dn) {
-        const uint16_t* r0 = &Vs[(32 * kk + 4 * g + tr_row) * KP + 16 * dn + tr_col];
-        vlo[kk][dn] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)r0);
-        vhi[kk][dn] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(r0 + 16 * KP));
-      }
-    // ---- causal mask + online softmax (query c of q-tile t; its keys sit on the 4 lanes g) --
-    // Only the tiles that straddle the diagonal need the mask; every other tile takes the lean
-    // path: max on the raw scores, then one fma + one exp2 per score.  The O^T rescale is skipped
-    // (exactly: alpha == 1) when no lane's running maximum moved.
-    const bool need_mask = tile * TK + TK - 1 > w_first_pos;
-    bf16x8_t pb[2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      float pv[16];
-      float mn, alpha, ps = 0.f;
-      if (need_mask) {
-        float mx = -INFINITY;
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            float sv = st[u][t][i] * scale_log2e;
-            if (tile * TK + 16 * u + 4 * g + i > qpos[t]) sv = -INFINITY;
-            st[u][t][i] = sv;
-            mx = fmaxf(mx, sv);
-          }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        mn = fmaxf(mrow[t], mx);
-        alpha = sexp2(mrow[t], mn);
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            pv[4 * u + i] = sexp2(st[u][t][i], mn);
-            ps += pv[4 * u + i];
-          }
-      } else {
-        float mx = st[0][t][0];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) mx = fmaxf(mx, st[u][t][i]);
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        mn = fmaxf(mrow[t], mx * scale_log2e);      // finite: every key of the tile is visible
-        alpha = fexp2(mrow[t] - mn);                // exp2(-inf) = 0 on the first tile
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            pv[4 * u + i] = fexp2(fmaf(st[u][t][i], scale_log2e, -mn));
-            ps += pv[4 * u + i];
-          }
-      }
-      const bool moved = mn != mrow[t];
-      mrow[t] = mn;
-      lrow[t] = lrow[t] * alpha + ps;
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        union { uint32_t w[4]; bf16x8_t v; } pk;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) pk.w[k] = pack_bf16x2(pv[8 * kk + 2 * k], pv[8 * kk + 2 * k + 1]);
-        pb[t][kk] = pk.v;
-      }
-      if (__any(moved)) {
-#pragma unroll
-        for (int dn = 0; dn < DN; ++dn) {
-          acc[t][dn][0] *= alpha; acc[t][dn][1] *= alpha; acc[t][dn][2] *= alpha; acc[t][dn][3] *= alpha;
-        }
-      }
-    }
-    // ---- O^T += V^T . P^T ----------------------------------------------------------------
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-      for (int dn = 0; dn < DN; ++dn) {
-        const s16x4_t lo = vlo[kk][dn], hi = vhi[kk][dn];
-        const bf16x8_t a = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        acc[0][dn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, pb[0][kk], acc[0][dn], 0, 0, 0);
-        acc[1][dn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, pb[1][kk], acc[1][dn], 0, 0, 0);
-      }
-    }
-  };
-  for (int tile = 0; tile < ntiles; tile += 2) {
-    do_tile(kregA, vregA, tile);
-    if (tile + 1 < ntiles) do_tile(kregB, vregB, tile + 1);
-  }
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    float lsum = lrow[t];
-    lsum += __shfl_xor(lsum, 16);
-    lsum += __shfl_xor(lsum, 32);
-    if (qok[t]) {
-      const float inv = 1.f / lsum;
-      uint16_t* orow = out + ((size_t)(q0 + 16 * t + c) * nh + head) * HD;
-#pragma unroll
-      for (int dn = 0; dn < DN; ++dn) {
-        const uint2 pk = make_uint2(pack_bf16x2(acc[t][dn][0] * inv, acc[t][dn][1] * inv),
-                                    pack_bf16x2(acc[t][dn][2] * inv, acc[t][dn][3] * inv));
-        *reinterpret_cast<uint2*>(orow + 16 * dn + 4 * g) = pk;
-      }
-    }
-  }
-  }  // pass
-}
-
-
-// =====================================================================================
-// context encoding, second generation: 32x32x16 MFMAs, K/V tiles by LDS-DMA, two waves per SIMD
-// =====================================================================================
-// What the counters of the kernel above asked for (17 % MFMA-busy at one wave per
+// What the counters of the first-generation kernel asked for (17 % MFMA-busy at one wave per
 // SIMD, 408 registers, 144 accumulator moves and a ds_write staging pass per 64-key tile):
 //   * a wave owns ONE 32-query block of one q head: S^T[key][q] = K . Q^T on v_mfma_f32_32x32x16_bf16
 //     puts a query on a lane (its 32 scores of a 64-key tile in 32 registers of lanes l and l + 32), so
@@ -993,19 +752,31 @@ __device__ __forceinline__ int kv_swz(int key) {   // XOR key of the 16-byte chu
   else return (((key >> 1) & 1) << 2) | ((key >> 2) & 3);                        // 128-byte rows,  8 chunks
 }
 
+// The sizes the two kernels and their launchers agree on.
+template <int HD>
+struct PrefillTile {
+  static constexpr int TK = 64;                // keys per tile
+  static constexpr int ROWB = HD * 2;          // bytes per K/V row of the bf16 image
+  static constexpr int KIMG = TK * ROWB;       // bf16 image of a K (or V) tile: 16 / 8 KiB
+  static constexpr int ISTAGE = 2 * KIMG;      // K image, V image
+  static constexpr int CSTAGE = 2 * TK * HD;   // the same tile as FP8 codes: K part, V part
+  static constexpr int NSTAGE = 3;             // stages of the DMA ring (of images in the bf16 kernel, of codes in the f8 kernel)
+};
+template <int HD>
+constexpr int attn_prefill_lds() { return PrefillTile<HD>::NSTAGE * PrefillTile<HD>::ISTAGE; }
+template <int HD>   // the code ring and a double-buffered image
+constexpr int attn_prefill_f8_lds() { return PrefillTile<HD>::NSTAGE * PrefillTile<HD>::CSTAGE + 2 * PrefillTile<HD>::ISTAGE; }
+
 template <int HD, int NW>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_prefill2_kernel(
     const uint16_t* __restrict__ q, int T, int q_pos0, const uint16_t* __restrict__ kpool,
     const uint16_t* __restrict__ vpool, int bs, int bs_shift, const int32_t* __restrict__ block_table, int nh, int nkv,
     int G, int Gp, int nblk, uint16_t* __restrict__ out, float scale_log2e) {
-  constexpr int TK = 64;                       // keys per tile
-  constexpr int ROWB = HD * 2;                 // bytes per K/V row
+  using P = PrefillTile<HD>;
+  constexpr int TK = P::TK, ROWB = P::ROWB, KBYTES = P::KIMG, STAGE = P::ISTAGE, NSTAGE = P::NSTAGE;
   constexpr int CPR = HD / 8;                  // 16-byte chunks per row
   constexpr int KPP = 1024 / ROWB;             // keys per 1 KiB DMA piece (4 / 8)
   constexpr int NP = TK / KPP;                 // pieces per K (or V) tile (16 / 8)
-  constexpr int KBYTES = TK * ROWB;            // 16 / 8 KiB
-  constexpr int STAGE = 2 * KBYTES;
-  constexpr int NSTAGE = 3;
   constexpr int PPW = NP / NW > 0 ? NP / NW : 1;   // K pieces per wave and tile (V the same)
   static_assert(NP % NW == 0, "pieces must divide over the waves");
   constexpr int CNT = 2 * PPW;                 // DMA instructions per wave and tile
@@ -1270,53 +1041,6 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   }
 }
 
-static bool attn_prefill_v1() {   // MI355X_ATTN_PREFILL_V1=1: the first-generation kernel (A/B)
-  static const bool on = [] { const char* v = getenv("MI355X_ATTN_PREFILL_V1"); return v && v[0] == '1'; }();
-  return on;
-}
-
-int launch_attn_prefill(const uint16_t* q, int T, int q_pos0, const uint16_t* kpool, const uint16_t* vpool,
-                        int block_size, const int32_t* block_table, int nh, int nkv, int hd, uint16_t* out,
-                        hipStream_t s) {
-  MI_CHECK(hd == 64 || hd == 128, "attention: head_dim must be 64 or 128");
-  MI_CHECK(T >= 1 && q_pos0 >= 0, "attention: bad T / q_pos0");
-  MI_CHECK(nh % nkv == 0 && nh / nkv <= 8, "attention: q heads per kv head must be 1..8");
-  MI_CHECK(ceil_div(q_pos0 + T, block_size) <= kPrefillMaxBlocks, "attention: context spans more than 4096 blocks");
-  const int G = nh / nkv;
-  const int Gp = G <= 1 ? 1 : (G <= 2 ? 2 : (G <= 4 ? 4 : 8));
-  const float scale_log2e = 1.4426950408889634f / sqrtf((float)hd);
-  if (!attn_prefill_v1()) {
-    // second generation: 8 waves = (8 / Gp) query blocks x Gp heads; blocks in complementary pairs
-    const int nblk = ceil_div(T, 32), npair = (nblk + 1) / 2, qb = 8 / Gp;
-    int bs_shift = -1;
-    for (int sh = 4; sh < 20; ++sh) if ((1 << sh) == block_size) bs_shift = sh;
-    const dim3 grid2(ceil_div(npair, qb >= 2 ? qb / 2 : 1), nkv);
-    if (hd == 128) {
-      constexpr int lds = 3 * 2 * 64 * 256;
-      MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_prefill2_kernel<128, 8>), lds));
-      hipLaunchKernelGGL((attn_prefill2_kernel<128, 8>), grid2, dim3(512), lds, s, q, T, q_pos0, kpool, vpool, block_size, bs_shift,
-                         block_table, nh, nkv, G, Gp, nblk, out, scale_log2e);
-    } else {
-      constexpr int lds = 3 * 2 * 64 * 128;
-      MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_prefill2_kernel<64, 8>), lds));
-      hipLaunchKernelGGL((attn_prefill2_kernel<64, 8>), grid2, dim3(512), lds, s, q, T, q_pos0, kpool, vpool, block_size, bs_shift,
-                         block_table, nh, nkv, G, Gp, nblk, out, scale_log2e);
-    }
-    MI_HIP(hipGetLastError());
-    return MI_OK;
-  }
-  const int waves = Gp < 4 ? 4 : Gp, QB = waves / Gp;
-  const int nqb = ceil_div(T, 32 * QB);
-  const int paired = nqb * nkv > 384 ? 1 : 0;   // more blocks than 1.5 per CU: pair complementary ones
-  const dim3 grid(paired ? ceil_div(nqb, 2) : nqb, nkv);
-#define MI_PF(HD_, W_) hipLaunchKernelGGL((attn_prefill_kernel<HD_, W_>), grid, dim3(W_ * 64), 0, s, q, T, q_pos0, kpool, vpool, block_size, block_table, nh, nkv, G, Gp, paired, out, scale_log2e)
-  if (hd == 128) { if (waves == 4) MI_PF(128, 4); else MI_PF(128, 8); }
-  else { if (waves == 4) MI_PF(64, 4); else MI_PF(64, 8); }
-#undef MI_PF
-  MI_HIP(hipGetLastError());
-  return MI_OK;
-}
-
 // =====================================================================================
 // context encoding over an FP8 (e4m3) pool
 // =====================================================================================
@@ -1347,17 +1071,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const uint16_t* __restrict__ q, int T, int q_pos0, const uint8_t* __restrict__ kpool,
     const uint8_t* __restrict__ vpool, int bs, int bs_shift, const int32_t* __restrict__ block_table, int nh, int nkv,
     int G, int Gp, int nblk, uint16_t* __restrict__ out, float score_scale, float v_scale) {
-  constexpr int TK = 64;                       // keys per tile
-  constexpr int ROWB = HD * 2;                 // bytes per K/V row of the bf16 image
+  using P = PrefillTile<HD>;
+  constexpr int TK = P::TK, ROWB = P::ROWB, KIMG = P::KIMG, ISTAGE = P::ISTAGE, CSTAGE = P::CSTAGE, NSTAGE = P::NSTAGE;
   constexpr int KPP = 1024 / HD;               // keys per 1 KiB piece of codes (8 / 16)
   constexpr int NP = TK / KPP;                 // pieces per K (or V) tile (8 / 4)
   constexpr int CPC = HD / 16;                 // 16-byte code chunks per row
   constexpr int PW = 2 * NP / NW;              // pieces per wave and tile (2 / 1) = DMA instructions per wave and tile
   static_assert(2 * NP % NW == 0 && PW >= 1, "the K and V pieces of a tile must divide over the waves");
-  constexpr int CSTAGE = 2 * TK * HD;          // code ring stage: K part, V part
-  constexpr int NSTAGE = 3;
-  constexpr int KIMG = TK * ROWB;              // bf16 image of a K (or V) tile
-  constexpr int ISTAGE = 2 * KIMG;
   constexpr int KSTEPS = HD / 16, DB = HD / 32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* const img = smem + NSTAGE * CSTAGE;
@@ -1648,35 +1368,62 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   }
 }
 
-int launch_attn_prefill_f8(const uint16_t* q, int T, int q_pos0, const uint8_t* kpool, const uint8_t* vpool,
-                           int block_size, const int32_t* block_table, int nh, int nkv, int hd, float k_scale,
-                           float v_scale, uint16_t* out, hipStream_t s) {
+// ---- launch ------------------------------------------------------------------------------------------------------
+// 8 waves = (8 / Gp) query blocks x Gp heads; blocks in complementary pairs
+struct PrefillLaunch {
+  int G, Gp, nblk, bs_shift;   // bs_shift: log2(block_size), -1 when it is no power of two
+  dim3 grid;
+  float scale_log2e;
+};
+static int prefill_launch_geometry(int T, int q_pos0, int block_size, int nh, int nkv, int hd, PrefillLaunch* g) {
   MI_CHECK(hd == 64 || hd == 128, "attention: head_dim must be 64 or 128");
   MI_CHECK(T >= 1 && q_pos0 >= 0, "attention: bad T / q_pos0");
   MI_CHECK(nh % nkv == 0 && nh / nkv <= 8, "attention: q heads per kv head must be 1..8");
-  MI_CHECK(block_size >= 16 && block_size % 16 == 0, "attention: block_size must be a multiple of 16");   // a DMA piece (8 / 16 keys) never straddles blocks
+  // mi_ctx_create holds max_model_len to the same bound, so a context that was created never meets this
   MI_CHECK(ceil_div(q_pos0 + T, block_size) <= kPrefillMaxBlocks, "attention: context spans more than 4096 blocks");
-  MI_CHECK(k_scale > 0.f && v_scale > 0.f, "attention: the FP8 KV scales must be positive");
-  const int G = nh / nkv;
-  const int Gp = G <= 1 ? 1 : (G <= 2 ? 2 : (G <= 4 ? 4 : 8));
-  const float score_scale = 1.4426950408889634f / sqrtf((float)hd) * k_scale;
-  const int nblk = ceil_div(T, 32), npair = (nblk + 1) / 2, qb = 8 / Gp;
-  int bs_shift = -1;
-  for (int sh = 4; sh < 20; ++sh) if ((1 << sh) == block_size) bs_shift = sh;
-  const dim3 grid(ceil_div(npair, qb >= 2 ? qb / 2 : 1), nkv);
-  if (hd == 128) {
-    constexpr int lds = 3 * 2 * 64 * 128 + 2 * 2 * 64 * 256;
-    MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_prefill_f8_kernel<128, 8>), lds));
-    hipLaunchKernelGGL((attn_prefill_f8_kernel<128, 8>), grid, dim3(512), lds, s, q, T, q_pos0, kpool, vpool, block_size, bs_shift,
-                       block_table, nh, nkv, G, Gp, nblk, out, score_scale, v_scale);
-  } else {
-    constexpr int lds = 3 * 2 * 64 * 64 + 2 * 2 * 64 * 128;
-    MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_prefill_f8_kernel<64, 8>), lds));
-    hipLaunchKernelGGL((attn_prefill_f8_kernel<64, 8>), grid, dim3(512), lds, s, q, T, q_pos0, kpool, vpool, block_size, bs_shift,
-                       block_table, nh, nkv, G, Gp, nblk, out, score_scale, v_scale);
-  }
-  MI_HIP(hipGetLastError());
+  g->G = nh / nkv;
+  g->Gp = g->G <= 1 ? 1 : (g->G <= 2 ? 2 : (g->G <= 4 ? 4 : 8));
+  g->nblk = ceil_div(T, 32);
+  const int npair = (g->nblk + 1) / 2, qb = 8 / g->Gp;
+  g->bs_shift = -1;
+  for (int sh = 4; sh < 20; ++sh) if ((1 << sh) == block_size) g->bs_shift = sh;
+  g->grid = dim3(ceil_div(npair, qb >= 2 ? qb / 2 : 1), nkv);
+  g->scale_log2e = 1.4426950408889634f / sqrtf((float)hd);
   return MI_OK;
+}
+
+int launch_attn_prefill(const uint16_t* q, int T, int q_pos0, const uint16_t* kpool, const uint16_t* vpool,
+                        int block_size, const int32_t* block_table, int nh, int nkv, int hd, uint16_t* out,
+                        hipStream_t s) {
+  PrefillLaunch g;
+  MI_TRY_A(prefill_launch_geometry(T, q_pos0, block_size, nh, nkv, hd, &g));
+  auto launch = [&](auto hd_c) -> int {
+    constexpr int HD = decltype(hd_c)::value, lds = attn_prefill_lds<HD>();
+    MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_prefill2_kernel<HD, 8>), lds));
+    hipLaunchKernelGGL((attn_prefill2_kernel<HD, 8>), g.grid, dim3(512), lds, s, q, T, q_pos0, kpool, vpool, block_size,
+                       g.bs_shift, block_table, nh, nkv, g.G, g.Gp, g.nblk, out, g.scale_log2e);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+  };
+  return hd == 128 ? launch(std::integral_constant<int, 128>{}) : launch(std::integral_constant<int, 64>{});
+}
+
+int launch_attn_prefill_f8(const uint16_t* q, int T, int q_pos0, const uint8_t* kpool, const uint8_t* vpool,
+                           int block_size, const int32_t* block_table, int nh, int nkv, int hd, float k_scale,
+                           float v_scale, uint16_t* out, hipStream_t s) {
+  MI_CHECK(block_size >= 16 && block_size % 16 == 0, "attention: block_size must be a multiple of 16");   // a DMA piece (8 / 16 keys) never straddles blocks
+  PrefillLaunch g;
+  MI_TRY_A(prefill_launch_geometry(T, q_pos0, block_size, nh, nkv, hd, &g));
+  MI_CHECK(k_scale > 0.f && v_scale > 0.f, "attention: the FP8 KV scales must be positive");
+  auto launch = [&](auto hd_c) -> int {
+    constexpr int HD = decltype(hd_c)::value, lds = attn_prefill_f8_lds<HD>();
+    MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_prefill_f8_kernel<HD, 8>), lds));
+    hipLaunchKernelGGL((attn_prefill_f8_kernel<HD, 8>), g.grid, dim3(512), lds, s, q, T, q_pos0, kpool, vpool, block_size,
+                       g.bs_shift, block_table, nh, nkv, g.G, g.Gp, g.nblk, out, g.scale_log2e * k_scale, v_scale);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+  };
+  return hd == 128 ? launch(std::integral_constant<int, 128>{}) : launch(std::integral_constant<int, 64>{});
 }
 
 // =====================================================================================
