@@ -95,13 +95,17 @@ typedef struct mi_model_config {
    * ignores them).  write: code = rne_e4m3(clamp(float(x_bf16) * (1.0f / scale), -448, 448)); read: float(code) * scale.
    * The scales are not part of the .miw images: a caller that restarts from mi_load_weights_file sends them again. */
   int32_t kv_cache_dtype;
+  /* Qwen3: an RMSNorm over head_dim with a learned gain on every q head and every k head, after the projection and
+   * before RoPE (gains: "model.layers.<l>.self_attn.q_norm.weight" / ".k_norm.weight", [head_dim]).  1 = the QKV
+   * projection leaves fp32 and mi_op_qk_norm_rope_kv's kernel follows it; 0 = everything as before. */
+  int32_t qk_norm;
 } mi_model_config;
 enum { MI_KV_BF16 = 0, MI_KV_F8E4M3 = 1 };
 #define MI_TP_ALL_RANKS (-1)
 enum { MI_TP_TRANSPORT_P2P = 0, MI_TP_TRANSPORT_RCCL = 1 };
 
 const char* mi_last_error(void);
-int mi_version(void);   /* 6 = this header (+ mi_op_paged_attn_prefill_f8: context encoding reads the FP8 pool natively); 5 lacked it (+ kv_cache_dtype and the FP8-KV entry points mi_op_kv_write_f8, mi_op_paged_attn_decode_f8, mi_op_kv_dequant_gather); 4 lacked them (+ mi_tp_plan, mi_tp_info); 3 lacked those; 2 lacked tp_device_ids / tp_transport / MI_TP_ALL_RANKS; 1 lacked mi_forward_tokens, mi_op_sample, mi_tp_init_transport */
+int mi_version(void);   /* 7 = this header (+ qk_norm, mi_op_qk_norm_rope_kv: Qwen3); 6 lacked them (+ mi_op_paged_attn_prefill_f8: context encoding reads the FP8 pool natively); 5 lacked it (+ kv_cache_dtype and the FP8-KV entry points mi_op_kv_write_f8, mi_op_paged_attn_decode_f8, mi_op_kv_dequant_gather); 4 lacked them (+ mi_tp_plan, mi_tp_info); 3 lacked those; 2 lacked tp_device_ids / tp_transport / MI_TP_ALL_RANKS; 1 lacked mi_forward_tokens, mi_op_sample, mi_tp_init_transport */
 
 int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out);
 int mi_ctx_destroy(mi_ctx* ctx);
@@ -382,6 +386,21 @@ int mi_op_kv_dequant_gather(const void* pool_u8, int32_t num_blocks, int32_t blo
                             const int32_t* block_table, int32_t MB, int32_t kv_len, int32_t nkv,
                             int32_t hd, float k_scale, float v_scale, void* staged_bf16,
                             void* stream);
+
+/* ---- Qwen3 per-head QK-norm (ABI 7) ------------------------------------------------------------
+ * What a context with qk_norm = 1 runs between the QKV projection and attention.  qkv [T, (nh + 2 nkv) * hd] fp32:
+ * the fused [q|k|v] projection in the library's column order (q and k heads pair-interleaved: column 2i of a head
+ * holds d = i, column 2i + 1 holds d = i + hd / 2; V plain).  gq, gk [hd] fp32 gains in the same interleaved order;
+ * pos, slots [T] int32 (slot -1 = no KV write); rope_cos / rope_sin [max_pos, hd / 2] fp32, max_pos > every pos.
+ * Per (token, head) of q and k: r = rsqrtf(sum(y^2) / hd + eps), z = (y * r) * g, RoPE in fp32, bf16 (RNE); q to
+ * q_out [T, nh * hd] bf16, k to the K pool row of slots[t]; V heads: bf16 (RNE), to the V pool.  pool: the layout of
+ * mi_op_kv_write (kv_dtype MI_KV_BF16) or of mi_op_kv_write_f8 with its write rule and k_scale / v_scale
+ * (MI_KV_F8E4M3).  An all-zero head gives zeros.  hd 64 or 128. */
+int mi_op_qk_norm_rope_kv(const float* qkv, const float* gq, const float* gk, const int32_t* pos,
+                          const int32_t* slots, int32_t T, int32_t nh, int32_t nkv, int32_t hd, float eps,
+                          const float* rope_cos, const float* rope_sin, void* q_out, void* pool,
+                          int32_t num_blocks, int32_t block_size, int32_t kv_dtype, float k_scale,
+                          float v_scale, void* stream);
 
 #ifdef __cplusplus
 }

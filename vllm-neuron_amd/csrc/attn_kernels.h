@@ -43,6 +43,16 @@ int launch_attn_prefill(const uint16_t* q, int T, int q_pos0, const uint16_t* kp
 int launch_kv_write(const uint16_t* k, const uint16_t* v, const int64_t* slots, int T, int nkv, int hd,
                     uint16_t* kpool, uint16_t* vpool, int block_size, hipStream_t s);
 
+// Qwen3: qkv [T, (nh + 2 nkv) * hd] fp32 (the fused projection with EPI_F32: q / k heads pair-interleaved, V plain) ->
+// per-head RMSNorm of every q and k head with gains gq / gk [hd] (interleaved like the columns), RoPE, bf16: q to
+// q_out [T, nh * hd], k and (un-normalised) v to the pool rows of slots [T] (-1, or a slot outside the pool, skips) --
+// the layout and dimension order EPI_QKV / EPI_QKV_F8 write.  f8: byte pools and the kv_quant4 write rule.
+// hd 64 or 128; rope_cos / rope_sin [max_pos, hd / 2] must cover every pos.
+int launch_qk_norm_rope_kv(const float* qkv, const float* gq, const float* gk, const int32_t* pos, const int32_t* slots,
+                           int T, int nh, int nkv, int hd, float eps, const float* rope_cos, const float* rope_sin,
+                           uint16_t* q_out, void* kpool, void* vpool, int num_blocks, int block_size, bool f8, float k_scale,
+                           float v_scale, hipStream_t s);
+
 // ---- FP8 (OCP e4m3fn) pool: [num_blocks][nkv][block_size][hd] BYTES per K / V, static scales --------------------
 // write: code = rne_e4m3(clamp(float(x_bf16) * (1.0f / scale), -448, 448)); read: value = float(code) * scale.
 // k, v [T, nkv, hd] bf16 -> byte pool at slots [T] (-1 skips)

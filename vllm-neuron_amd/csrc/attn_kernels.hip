@@ -1482,6 +1482,86 @@ int launch_kv_write_f8(const uint16_t* k, const uint16_t* v, const int64_t* slot
   return MI_OK;
 }
 
+// =====================================================================================
+// per-head QK-norm + RoPE + q buffer / KV-pool write (Qwen3)
+// =====================================================================================
+// qkv [T, (nh + 2 nkv) * HD] fp32 is the fused projection as EPI_F32 leaves it: q and k heads pair-interleaved
+// (column 2i <- d = i, 2i + 1 <- d = i + HD/2), V plain.  A lane owns one float4 of one (token, head) row = two
+// rotation pairs, the unit of the 8-byte q / K stores and of kv_quant4; a row is HD/4 lanes (32 or 16), a wave holds
+// 2 or 4 rows.  The (token, head) rows are flattened over the grid, so an odd head count (7 q + 2 kv) leaves no lane
+// group idle and a wave may hold the last heads of one token and the first of the next: every lane group reads its
+// own pos / slot.  Loads, in request order: pos + slot, the row and its gain, then cos / sin (they hang off pos, not
+// off the reduction); the sum of squares goes through DPP inside the row's lanes.  No LDS, no barrier.
+//   q, k:  z = (y * rsqrtf(sum(y^2) / HD + eps)) * g -> RoPE in fp32 (as epilogue_store<EPI_QKV>) -> bf16 (RNE)
+//   v:     bf16 (RNE)
+// An all-zero row (a padding q head of a TP shard) has r = rsqrtf(eps), finite: it stays zero.
+template <bool F8, int HD>
+__global__ __launch_bounds__(256) void qk_norm_rope_kv_kernel(
+    const float* __restrict__ qkv, const float* __restrict__ gq, const float* __restrict__ gk,
+    const int32_t* __restrict__ pos, const int32_t* __restrict__ slots, int rows, int nh, int nkv, float eps,
+    const float* __restrict__ rope_cos, const float* __restrict__ rope_sin, uint16_t* __restrict__ q_out,
+    void* __restrict__ kpool, void* __restrict__ vpool, int nslots, int bs, float k_inv, float v_inv) {
+  constexpr int LPR = HD / 4;                       // lanes per (token, head) row
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int row = tid / LPR, c = (tid % LPR) * 4;   // c: first of the lane's four columns inside the head
+  const bool live = row < rows;                     // whole lane groups are live or not
+  const int nht = nh + 2 * nkv;
+  const int t = live ? row / nht : 0, h = live ? row % nht : 0;
+  const bool is_q = h < nh, is_qk = h < nh + nkv;
+  const int p = max(pos[t], 0), slot = slots[t];
+  float4 y = make_float4(0.f, 0.f, 0.f, 0.f), g = y;
+  float2 cs = make_float2(1.f, 1.f), sn = make_float2(0.f, 0.f);
+  if (live) y = *reinterpret_cast<const float4*>(qkv + ((size_t)t * nht + h) * HD + c);
+  if (live && is_qk) {
+    g = *reinterpret_cast<const float4*>((is_q ? gq : gk) + c);
+    cs = *reinterpret_cast<const float2*>(rope_cos + (size_t)p * (HD / 2) + (c >> 1));
+    sn = *reinterpret_cast<const float2*>(rope_sin + (size_t)p * (HD / 2) + (c >> 1));
+  }
+  float ss = group_sum<16>(y.x * y.x + y.y * y.y + y.z * y.z + y.w * y.w);
+  if (LPR == 32) ss += __shfl_xor(ss, 16);
+  if (!live) return;
+  if (is_qk) {
+    const float r = rsqrtf(ss * (1.0f / HD) + eps);
+    const float z0 = (y.x * r) * g.x, z1 = (y.y * r) * g.y, z2 = (y.z * r) * g.z, z3 = (y.w * r) * g.w;
+    y.x = z0 * cs.x - z1 * sn.x; y.y = z1 * cs.x + z0 * sn.x;
+    y.z = z2 * cs.y - z3 * sn.y; y.w = z3 * cs.y + z2 * sn.y;
+  }
+  const uint2 packed = make_uint2(pack_bf16x2(y.x, y.y), pack_bf16x2(y.z, y.w));
+  if (is_q) {
+    *reinterpret_cast<uint2*>(q_out + ((size_t)t * nh + h) * HD + c) = packed;
+  } else if (slot >= 0 && slot < nslots) {
+    const int head = is_qk ? h - nh : h - nh - nkv;
+    const size_t at = (((size_t)(slot / bs) * nkv + head) * bs + slot % bs) * HD + c;
+    if (F8) *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(is_qk ? kpool : vpool) + at) = kv_quant4(packed, is_qk ? k_inv : v_inv);
+    else *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(is_qk ? kpool : vpool) + at) = packed;
+  }
+}
+
+int launch_qk_norm_rope_kv(const float* qkv, const float* gq, const float* gk, const int32_t* pos, const int32_t* slots,
+                           int T, int nh, int nkv, int hd, float eps, const float* rope_cos, const float* rope_sin,
+                           uint16_t* q_out, void* kpool, void* vpool, int num_blocks, int block_size, bool f8, float k_scale,
+                           float v_scale, hipStream_t s) {
+  MI_CHECK(hd == 64 || hd == 128, "qk_norm_rope_kv: head_dim must be 64 or 128");
+  MI_CHECK(T >= 0 && nh >= 1 && nkv >= 1 && num_blocks >= 1 && block_size >= 1, "qk_norm_rope_kv: bad geometry");
+  MI_CHECK((size_t)T * (nh + 2 * nkv) * (hd / 4) < ((size_t)1 << 31) && (size_t)num_blocks * block_size < ((size_t)1 << 31),
+           "qk_norm_rope_kv: too many rows / slots");
+  MI_CHECK(!f8 || (k_scale > 0.f && v_scale > 0.f), "qk_norm_rope_kv: FP8 KV scales must be positive");
+  if (T == 0) return MI_OK;
+  const int rows = T * (nh + 2 * nkv), lanes = rows * (hd / 4);
+  // a token-generation step is a few hundred rows: one wave per work-group spreads them over the CUs; a context-encoding
+  // bucket streams through 4-wave work-groups
+  const int block = lanes >= 64 * 1024 ? 256 : 64;
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(ceil_div(lanes, block)), dim3(block), 0, s, qkv, gq, gk, pos, slots, rows, nh, nkv, eps,
+                       rope_cos, rope_sin, q_out, kpool, vpool, num_blocks * block_size, block_size,
+                       f8 ? 1.0f / k_scale : 1.f, f8 ? 1.0f / v_scale : 1.f);
+  };
+  if (hd == 128) f8 ? launch(qk_norm_rope_kv_kernel<true, 128>) : launch(qk_norm_rope_kv_kernel<false, 128>);
+  else f8 ? launch(qk_norm_rope_kv_kernel<true, 64>) : launch(qk_norm_rope_kv_kernel<false, 64>);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
 // ---- FP8 pool -> bf16 staging pool for context encoding ---------------------------------------------------------
 // The blocks of ONE sequence, in block-table order: staged [2][nblk][nkv][bs][hd] bf16 = bf16_rne(float(code) * scale).
 // A (block, all heads) range is contiguous in both pools, so a thread widens 16 codes (one 16-byte load, two 16-byte

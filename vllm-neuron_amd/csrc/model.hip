@@ -11,6 +11,10 @@
 //   gemv[O proj -> fp32 partial]                     (+ RCCL all-reduce when tp_degree > 1)
 //   gemv[residual add + norm -> gate|up -> SwiGLU]
 //   gemv[down proj -> fp32 partial]                  (+ RCCL all-reduce)
+// With cfg.qk_norm (Qwen3: RMSNorm over head_dim on every q and k head, before RoPE) the first launch is two: a head's
+// 128 outputs span 8 row-tiles of the weight stream, usually in different work-groups, so the projection leaves fp32
+//   gemv[norm -> QKV -> bias -> fp32 [rows, q_dim + 2 kv_dim]] ; qk_norm_rope_kv[per-head norm -> RoPE -> q buffer + KV-pool scatter]
+// and everything behind it (attention, hipGraph capture, ragged batches, speculation, TP shards) is unchanged.
 // The residual stream is fp32 and ping-pongs between two buffers: the norm prologue of the
 // NEXT kernel folds in the previous partial, so a row-parallel output needs no extra pass.
 
@@ -281,7 +285,18 @@ int run_layers(mi_ctx* c, int rows, bool decode, int B, int MB, int q_pos0, int 
       e.pos = c->d_pos; e.slots = c->d_slots; e.rope_cos = c->rope_cos; e.rope_sin = c->rope_sin;
       e.kpool = kpool; e.vpool = vpool; e.block_size = k.block_size;
       e.k_inv = 1.0f / ksc; e.v_inv = 1.0f / vsc;
-      MI_TRY(run_linear(c, W.qkv, rows, PRO_NORM, p, f8 ? EPI_QKV_F8 : EPI_QKV, e));
+      if (k.qk_norm) {   // Qwen3: a head's reduction spans tiles of several work-groups: fp32 out, then norm + RoPE + q / KV write in a kernel of its own
+        EpiArgs ef{};
+        ef.out_f32 = c->qkv_f32; ef.ld_out = c->q_dim + 2 * c->kv_dim;
+        MI_TRY(run_linear(c, W.qkv, rows, PRO_NORM, p, EPI_F32, ef));
+        if (c->runs(MI_K_OTHER)) {
+          Scope sc(c, MI_K_OTHER);
+          MI_TRY(launch_qk_norm_rope_kv(c->qkv_f32, W.g_qn, W.g_kn, c->d_pos, c->d_slots, rows, c->nh_l, c->nkv_l, c->hd, k.rms_norm_eps,
+                                        c->rope_cos, c->rope_sin, c->qbuf, kpool, vpool, k.num_blocks, k.block_size, f8, ksc, vsc, s));
+        }
+      } else {
+        MI_TRY(run_linear(c, W.qkv, rows, PRO_NORM, p, f8 ? EPI_QKV_F8 : EPI_QKV, e));
+      }
       if (have_partial) cur ^= 1;
     }
     if (decode && !c->runs(MI_K_ATTN_DECODE)) {
@@ -547,6 +562,15 @@ int route_vector(mi_ctx* c, const std::string& name, const std::vector<float>& v
   LayerW& W = c->layers[l];
   if (ends_with(name, "input_layernorm.weight")) { MI_CHECK(n == c->H, "input_layernorm shape"); return place_vector(c, W.g_in, v.data(), n); }
   if (ends_with(name, "post_attention_layernorm.weight")) { MI_CHECK(n == c->H, "post_attention_layernorm shape"); return place_vector(c, W.g_post, v.data(), n); }
+  const bool qn = ends_with(name, "self_attn.q_norm.weight"), kn = ends_with(name, "self_attn.k_norm.weight");
+  if (qn || kn) {   // Qwen3 per-head gains [hd], the same on every head and every rank: into the columns' pair-interleaved order
+    MI_CHECK(k.qk_norm != 0, "q_norm / k_norm tensor given but the config has qk_norm = 0");
+    const int hd = c->hd;
+    MI_CHECK(n == hd, "q_norm / k_norm shape");
+    std::vector<float> out(hd);
+    for (int d = 0; d < hd; ++d) out[d < hd / 2 ? 2 * d : 2 * (d - hd / 2) + 1] = v[d];
+    return place_vector(c, qn ? W.g_qn : W.g_kn, out.data(), hd);
+  }
   const bool qb = ends_with(name, "self_attn.q_proj.bias"), kb = ends_with(name, "self_attn.k_proj.bias"),
              vb = ends_with(name, "self_attn.v_proj.bias");
   if (qb || kb || vb) {
@@ -611,7 +635,7 @@ int capture_or_launch_decode(mi_ctx* c, int B, int MB) {
 extern "C" {
 
 const char* mi_last_error(void) { return mi::g_err.c_str(); }
-int mi_version(void) { return 6; }   // 6: + mi_op_paged_attn_prefill_f8; 5: + kv_cache_dtype, mi_op_kv_write_f8 / mi_op_paged_attn_decode_f8 / mi_op_kv_dequant_gather; 4: + mi_tp_plan, mi_tp_info; 3: + in-process tensor parallelism (tp_rank = MI_TP_ALL_RANKS, tp_device_ids, tp_transport)
+int mi_version(void) { return 7; }   // 7: + qk_norm, mi_op_qk_norm_rope_kv (Qwen3); 6: + mi_op_paged_attn_prefill_f8; 5: + kv_cache_dtype, mi_op_kv_write_f8 / mi_op_paged_attn_decode_f8 / mi_op_kv_dequant_gather; 4: + mi_tp_plan, mi_tp_info; 3: + in-process tensor parallelism (tp_rank = MI_TP_ALL_RANKS, tp_device_ids, tp_transport)
 
 int mi_tp_plan(const mi_model_config* cfg, int32_t rank, mi_tp_plan_t* out) {
   MI_CHECK(cfg && out, "null argument");
@@ -678,6 +702,7 @@ int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out) {
   MI_CHECK(k.weight_dtype >= MI_W_BF16 && k.weight_dtype <= MI_W_INT8, "weight_dtype");
   MI_CHECK(k.quant_type == MI_Q_PER_TENSOR_SYMMETRIC || k.quant_type == MI_Q_PER_CHANNEL_SYMMETRIC, "quant_type");
   MI_CHECK(k.kv_cache_dtype == MI_KV_BF16 || k.kv_cache_dtype == MI_KV_F8E4M3, "kv_cache_dtype");
+  MI_CHECK(k.qk_norm == 0 || k.qk_norm == 1, "qk_norm");
   int ndev = 0;
   MI_HIP(hipGetDeviceCount(&ndev));
   MI_CHECK(ndev > 0, "no HIP device: this library has no CPU fallback");
@@ -723,6 +748,10 @@ int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out) {
     MI_TRY(alloc_linear(c, W.down, c->H, c->I_l, wd, false));
     MI_TRY(dmalloc(&W.g_in, (size_t)c->H, &c->weight_bytes));
     MI_TRY(dmalloc(&W.g_post, (size_t)c->H, &c->weight_bytes));
+    if (k.qk_norm) {
+      MI_TRY(dmalloc(&W.g_qn, (size_t)c->hd, &c->weight_bytes));
+      MI_TRY(dmalloc(&W.g_kn, (size_t)c->hd, &c->weight_bytes));
+    }
   }
   MI_TRY(alloc_linear(c, c->lm_head, c->V_l, c->H, k.quantize_lm_head ? wd : MI_W_BF16, false));
   MI_TRY(dmalloc(&c->g_final, (size_t)c->H, &c->weight_bytes));
@@ -749,11 +778,11 @@ int mi_ctx_destroy(mi_ctx* c) {
   if (c->comm) ncclCommDestroy(c->comm);
   if (c->grp && c->grp->lockstep && c->cfg.tp_rank != 0) hipStreamSynchronize(c->stream);
   auto fl = [](Linear& L) { hipFree(L.w); hipFree(L.scale); hipFree(L.bias); };
-  for (auto& W : c->layers) { fl(W.qkv); fl(W.o); fl(W.gu); fl(W.down); hipFree(W.g_in); hipFree(W.g_post); }
+  for (auto& W : c->layers) { fl(W.qkv); fl(W.o); fl(W.gu); fl(W.down); hipFree(W.g_in); hipFree(W.g_post); hipFree(W.g_qn); hipFree(W.g_kn); }
   fl(c->lm_head);
   void* ptrs[] = {c->g_final, c->embed, c->rowmax, c->kv_pool, c->rope_cos, c->rope_sin, c->stage_raw, c->stage_f32,
                   c->resid[0], c->resid[1], c->partial, c->xn, c->qbuf, c->attn_out, c->act, c->logits, c->logits_all,
-                  c->attn_scratch, c->kv_stage, c->d_ident, c->d_inputs, c->d_dec, c->d_dec_bt, c->d_sparams, c->d_tokens, c->x8, c->x8_scale, c->splitk_ws, c->d_spec, c->d_sample_scratch};
+                  c->attn_scratch, c->kv_stage, c->d_ident, c->d_inputs, c->d_dec, c->d_dec_bt, c->d_sparams, c->d_tokens, c->x8, c->x8_scale, c->splitk_ws, c->d_spec, c->d_sample_scratch, c->qkv_f32};
   for (void* p : ptrs) hipFree(p);
   void* hptrs[] = {c->h_inputs, c->h_dec, c->h_dec_bt, c->h_sparams, c->h_tokens, c->h_logits, c->h_spec};
   for (void* p : hptrs) if (p) hipHostFree(p);
@@ -844,6 +873,10 @@ int mi_init_synthetic_weights(mi_ctx* c, uint64_t seed, float std) {
     }
     MI_TRY(launch_fill_f32(c->layers[l].g_in, c->H, 1.0f, c->stream));
     MI_TRY(launch_fill_f32(c->layers[l].g_post, c->H, 1.0f, c->stream));
+    if (k.qk_norm) {
+      MI_TRY(launch_fill_f32(c->layers[l].g_qn, c->hd, 1.0f, c->stream));
+      MI_TRY(launch_fill_f32(c->layers[l].g_kn, c->hd, 1.0f, c->stream));
+    }
   }
   MI_TRY(launch_fill_f32(c->g_final, c->H, 1.0f, c->stream));
   if (!k.tie_word_embeddings) MI_TRY(gen("lm_head.weight", k.vocab_size, c->H, std));
@@ -863,8 +896,9 @@ struct ArtifactHeader {
   int32_t tile_format;      // of the weight tiling (mi_common.h): bump when the kernels' layout changes
   int32_t geo[9];           // layers, hidden, heads, kv heads, head dim, intermediate, vocab, qkv_bias, tie
   int32_t weight_dtype, quant_type, quantize_lm_head, tp_degree, tp_rank;
+  int32_t qk_norm;          // (layout version 2) the images hold the per-head q / k norm gains
 };
-constexpr int32_t kArtifactVersion = 1, kTileFormat = 1;
+constexpr int32_t kArtifactVersion = 2, kTileFormat = 1;
 
 void make_header(const mi_ctx* c, ArtifactHeader& h) {
   const mi_model_config& k = c->cfg;
@@ -877,6 +911,7 @@ void make_header(const mi_ctx* c, ArtifactHeader& h) {
   memcpy(h.geo, g, sizeof g);
   h.weight_dtype = k.weight_dtype; h.quant_type = k.quant_type; h.quantize_lm_head = k.quantize_lm_head;
   h.tp_degree = k.tp_degree; h.tp_rank = k.tp_rank;
+  h.qk_norm = k.qk_norm;
 }
 
 // every device tensor of a rank, in file order
@@ -890,6 +925,10 @@ void artifact_tensors(mi_ctx* c, std::vector<std::pair<void*, size_t>>& out) {
     lin(W.qkv); lin(W.o); lin(W.gu); lin(W.down);
     out.push_back({W.g_in, (size_t)c->H * 4});
     out.push_back({W.g_post, (size_t)c->H * 4});
+    if (W.g_qn) {
+      out.push_back({W.g_qn, (size_t)c->hd * 4});
+      out.push_back({W.g_kn, (size_t)c->hd * 4});
+    }
   }
   lin(c->lm_head);
   out.push_back({c->g_final, (size_t)c->H * 4});
@@ -997,6 +1036,7 @@ static size_t workspace_estimate(const mi_ctx* c) {
   const size_t R = (size_t)c->max_rows, H = (size_t)c->H;
   size_t b = 3 * R * H * 4 + R * std::max<size_t>(H, c->I_l) * 2 + 2 * R * c->q_dim * 2 + R * c->I_l * 2;
   if (k.prefill_fp8_activations) b += R * std::max<size_t>(std::max<size_t>(H, c->I_l), c->q_dim) + R * 4;
+  if (k.qk_norm) b += R * (c->q_dim + 2 * (size_t)c->kv_dim) * 4;            // fp32 QKV in front of the per-head norm
   b += (size_t)64 << 20;                                                   // split-K workspace
   b += (size_t)k.max_num_seqs * c->V_l * 4 * (1 + (k.tp_degree > 1 ? k.tp_degree : 0));
   b += attn_scratch_bytes(k.max_num_seqs, c->nh_l, c->hd);
@@ -1095,6 +1135,7 @@ int mi_finalize(mi_ctx* c) {
   MI_TRY(dmalloc(&c->qbuf, R * c->q_dim, ws));
   MI_TRY(dmalloc(&c->attn_out, R * c->q_dim, ws));
   MI_TRY(dmalloc(&c->act, R * c->I_l, ws));
+  if (k.qk_norm) MI_TRY(dmalloc(&c->qkv_f32, R * (c->q_dim + 2 * c->kv_dim), ws));
   if (k.prefill_fp8_activations) {
     MI_TRY(dmalloc(&c->x8, R * std::max(std::max(c->H, c->I_l), c->q_dim), ws));
     MI_TRY(dmalloc(&c->x8_scale, R, ws));
@@ -1931,6 +1972,20 @@ int mi_op_kv_dequant_gather(const void* pool_u8, int32_t num_blocks, int32_t blo
   MI_CHECK(k_scale > 0.f && v_scale > 0.f, "kv_dequant_gather: FP8 KV scales must be positive");
   return launch_kv_dequant_gather(reinterpret_cast<const uint8_t*>(pool_u8), num_blocks, block_size, block_table, MB, kv_len,
                                   nkv, hd, k_scale, v_scale, reinterpret_cast<uint16_t*>(staged_bf16), (hipStream_t)stream);
+}
+int mi_op_qk_norm_rope_kv(const float* qkv, const float* gq, const float* gk, const int32_t* pos, const int32_t* slots,
+                          int32_t T, int32_t nh, int32_t nkv, int32_t hd, float eps, const float* rope_cos,
+                          const float* rope_sin, void* q_out, void* pool, int32_t num_blocks, int32_t block_size,
+                          int32_t kv_dtype, float k_scale, float v_scale, void* stream) {
+  MI_CHECK(qkv && gq && gk && pos && slots && rope_cos && rope_sin && q_out && pool, "null argument");
+  MI_CHECK(kv_dtype == MI_KV_BF16 || kv_dtype == MI_KV_F8E4M3, "kv_dtype");
+  MI_CHECK(hd == 64 || hd == 128, "head_dim must be 64 or 128");
+  MI_CHECK(nkv >= 1 && num_blocks >= 1 && block_size >= 1, "qk_norm_rope_kv: empty pool");
+  const bool f8 = kv_dtype == MI_KV_F8E4M3;
+  const size_t half = (size_t)num_blocks * nkv * block_size * hd * (f8 ? 1 : 2);   // bytes of the K pool
+  return launch_qk_norm_rope_kv(qkv, gq, gk, pos, slots, T, nh, nkv, hd, eps, rope_cos, rope_sin,
+                                reinterpret_cast<uint16_t*>(q_out), pool, reinterpret_cast<uint8_t*>(pool) + half, num_blocks,
+                                block_size, f8, k_scale, v_scale, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -24,6 +24,7 @@ struct LayerW {
   Linear qkv, o, gu, down;
   float* g_in = nullptr;
   float* g_post = nullptr;
+  float *g_qn = nullptr, *g_kn = nullptr;   // qk_norm: per-head q / k norm gains [hd], pair-interleaved like the columns
 };
 
 struct Prof {
@@ -72,6 +73,7 @@ struct mi_ctx {
   float* resid[2] = {nullptr, nullptr};
   float* partial = nullptr;
   uint16_t *xn = nullptr, *qbuf = nullptr, *attn_out = nullptr, *act = nullptr;
+  float* qkv_f32 = nullptr;     // qk_norm: the QKV projection as fp32 [rows, q_dim + 2 kv_dim], input of the per-head norm
   uint8_t* x8 = nullptr;        // FP8-activation GEMM input [rows, K]
   float* x8_scale = nullptr;    // its per-token scales [rows]
   float* splitk_ws = nullptr;   // fp32 K-split slabs of short-prompt GEMMs

@@ -22,4 +22,4 @@ TORCH_DTYPE_TO_MI355X_AMP = _amp_table()
 # served through multimodal model classes by the reference: out of this backend's scope
 MI355X_MULTI_MODAL_MODELS = [f"{family}ForConditionalGeneration" for family in ("Mllama", "Llava", "Llama4")]
 
-SUPPORTED_ARCHITECTURES = ("LlamaForCausalLM", "Qwen2ForCausalLM", "MistralForCausalLM")
+SUPPORTED_ARCHITECTURES = ("LlamaForCausalLM", "Qwen2ForCausalLM", "MistralForCausalLM", "Qwen3ForCausalLM")

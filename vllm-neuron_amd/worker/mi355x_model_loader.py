@@ -505,7 +505,9 @@ def _decoder_geometry(hf) -> dict:
         rope_high_freq_factor=float(rs["high_freq_factor"]) if llama3 else 4.0,
         rope_original_max_position=int(rs["original_max_position_embeddings"]) if llama3 else 0,
         qkv_bias=int(getattr(hf, "model_type", "") == "qwen2" or bool(getattr(hf, "attention_bias", False))),
-        tie_word_embeddings=int(bool(getattr(hf, "tie_word_embeddings", False))))
+        tie_word_embeddings=int(bool(getattr(hf, "tie_word_embeddings", False))),
+        # Qwen3: RMSNorm over head_dim on every q and k head (self_attn.q_norm / k_norm) before RoPE
+        qk_norm=int(getattr(hf, "model_type", "") == "qwen3"))
 
 
 def _get_model_configs(config) -> tuple[str, int, int]:
