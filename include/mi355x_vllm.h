@@ -99,13 +99,18 @@ typedef struct mi_model_config {
    * before RoPE (gains: "model.layers.<l>.self_attn.q_norm.weight" / ".k_norm.weight", [head_dim]).  1 = the QKV
    * projection leaves fp32 and mi_op_qk_norm_rope_kv's kernel follows it; 0 = everything as before. */
   int32_t qk_norm;
+  /* Sliding-window attention (Mistral): a query at position p attends the keys p - W < k <= p, W keys with itself, in
+   * every layer.  0 = none (everything as before); a value >= max_model_len is treated as 0; negative: MI_EINVAL.
+   * Token generation walks only the K/V tiles the window touches, context encoding takes the windowed launch geometry
+   * once a sequence's keys outgrow W.  Blocks outside the window stay the caller's to keep or free. */
+  int32_t sliding_window;
 } mi_model_config;
 enum { MI_KV_BF16 = 0, MI_KV_F8E4M3 = 1 };
 #define MI_TP_ALL_RANKS (-1)
 enum { MI_TP_TRANSPORT_P2P = 0, MI_TP_TRANSPORT_RCCL = 1 };
 
 const char* mi_last_error(void);
-int mi_version(void);   /* 7 = this header (+ qk_norm, mi_op_qk_norm_rope_kv: Qwen3); 6 lacked them (+ mi_op_paged_attn_prefill_f8: context encoding reads the FP8 pool natively); 5 lacked it (+ kv_cache_dtype and the FP8-KV entry points mi_op_kv_write_f8, mi_op_paged_attn_decode_f8, mi_op_kv_dequant_gather); 4 lacked them (+ mi_tp_plan, mi_tp_info); 3 lacked those; 2 lacked tp_device_ids / tp_transport / MI_TP_ALL_RANKS; 1 lacked mi_forward_tokens, mi_op_sample, mi_tp_init_transport */
+int mi_version(void);   /* 8 = this header (+ sliding_window, mi_op_paged_attn_decode_sw, mi_op_paged_attn_prefill_sw: Mistral); 7 lacked them (+ qk_norm, mi_op_qk_norm_rope_kv: Qwen3); 6 lacked them (+ mi_op_paged_attn_prefill_f8: context encoding reads the FP8 pool natively); 5 lacked it (+ kv_cache_dtype and the FP8-KV entry points mi_op_kv_write_f8, mi_op_paged_attn_decode_f8, mi_op_kv_dequant_gather); 4 lacked them (+ mi_tp_plan, mi_tp_info); 3 lacked those; 2 lacked tp_device_ids / tp_transport / MI_TP_ALL_RANKS; 1 lacked mi_forward_tokens, mi_op_sample, mi_tp_init_transport */
 
 int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out);
 int mi_ctx_destroy(mi_ctx* ctx);
@@ -373,7 +378,9 @@ int mi_op_paged_attn_decode_f8(const void* q, const void* pool_u8, int32_t num_b
  * read, and no bf16 copy of the sequence exists in memory.  k_scale is folded into the score
  * scale, v_scale applied once to the normalised output.  block_size must be a multiple of 16.
  * A context with kv_cache_dtype = MI_KV_F8E4M3 runs it for context encoding when
- * MI355X_ATTN_PREFILL_F8_NATIVE=1 is set; its default is the staged form below. */
+ * MI355X_ATTN_PREFILL_F8_NATIVE=1 is set; its default is the staged form below.  The kernel has no
+ * sliding-window variant: a context with sliding_window = W ignores the switch for every call
+ * whose kv_len = q_pos0 + T exceeds W and takes the staged form. */
 int mi_op_paged_attn_prefill_f8(const void* q, int32_t T, int32_t q_pos0, const void* pool_u8,
                                 int32_t num_blocks, int32_t block_size, const int32_t* block_table,
                                 int32_t MB, int32_t nh, int32_t nkv, int32_t hd, float k_scale,
@@ -401,6 +408,22 @@ int mi_op_qk_norm_rope_kv(const float* qkv, const float* gq, const float* gk, co
                           const float* rope_cos, const float* rope_sin, void* q_out, void* pool,
                           int32_t num_blocks, int32_t block_size, int32_t kv_dtype, float k_scale,
                           float v_scale, void* stream);
+
+/* ---- Sliding-window attention (ABI 8) -----------------------------------------------------------
+ * What a context with sliding_window = W runs.  window = 0 is the unwindowed kernel of the pool type.
+ * Token generation: mi_op_paged_attn_decode (kv_dtype MI_KV_BF16; k_scale / v_scale ignored) or
+ * mi_op_paged_attn_decode_f8 (MI_KV_F8E4M3) where row b attends the keys ctx_lens[b] - window <= k < ctx_lens[b].
+ * Only the 32-token (FP8: 64-token) tiles from max(0, ctx_lens[b] - window) on are read.  Same scratch size. */
+int mi_op_paged_attn_decode_sw(const void* q, const void* pool, int32_t num_blocks, int32_t block_size,
+                               const int32_t* block_table, int32_t MB, const int32_t* ctx_lens, int32_t B,
+                               int32_t nh, int32_t nkv, int32_t hd, int32_t kv_dtype, float k_scale,
+                               float v_scale, int32_t window, void* out, void* scratch, void* stream);
+/* Context encoding over the bf16 pool: mi_op_paged_attn_prefill where the query at position p attends the keys
+ * p - window < k <= p.  q_pos0 + T <= window takes the unwindowed kernel (bit-identical output); beyond that a
+ * work-group owns adjacent 32-query blocks and streams only the key tiles of their band. */
+int mi_op_paged_attn_prefill_sw(const void* q, int32_t T, int32_t q_pos0, const void* pool, int32_t num_blocks,
+                                int32_t block_size, const int32_t* block_table, int32_t MB, int32_t nh,
+                                int32_t nkv, int32_t hd, int32_t window, void* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -42,7 +42,7 @@ class MiModelConfig(C.Structure):
         ("tp_degree", C.c_int32), ("tp_rank", C.c_int32), ("device_id", C.c_int32),
         ("use_graphs", C.c_int32), ("prefill_fp8_activations", C.c_int32),
         ("tp_device_ids", C.c_int32 * 16), ("tp_transport", C.c_int32),
-        ("kv_cache_dtype", C.c_int32), ("qk_norm", C.c_int32),
+        ("kv_cache_dtype", C.c_int32), ("qk_norm", C.c_int32), ("sliding_window", C.c_int32),
     ]
 
 
@@ -145,6 +145,12 @@ _SIGS = {
     "mi_op_qk_norm_rope_kv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p]),
+    "mi_op_paged_attn_decode_sw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                             C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_op_paged_attn_prefill_sw": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                              C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

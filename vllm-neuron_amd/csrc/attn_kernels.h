@@ -24,7 +24,9 @@ size_t attn_scratch_bytes(int B, int nh, int hd);
 int launch_attn_decode(const uint16_t* q, const uint16_t* kpool, const uint16_t* vpool, int block_size,
                        const int32_t* block_table, int MB, const int32_t* ctx_lens, int B, int nh,
                        int nkv, int hd, uint16_t* out, void* scratch, hipStream_t s, bool tickets_zeroed = false,
-                       int rows_per_seq = 1, int num_blocks = 0);
+                       int rows_per_seq = 1, int num_blocks = 0, int window = 0);
+// window W > 0 (sliding-window attention): row b attends the keys ctx_lens[b] - W <= k < ctx_lens[b] and the waves walk only
+// the tiles the window touches (windowed instantiations: split + combine, no in-launch merge, no early K/V request)
 // num_blocks > 0 (blocks of the pool): a wave's first K/V request does not wait for the context length (ids clamped into the pool)
 // rows_per_seq R > 1: batch rows b R .. b R + R - 1 are one sequence at consecutive positions (block_table row b R
 // serves them all); their heads share the MFMA columns and the sequence's K/V is read once
@@ -37,7 +39,10 @@ int launch_attn_decode(const uint16_t* q, const uint16_t* kpool, const uint16_t*
 constexpr int kPrefillMaxBlocks = 4096;
 int launch_attn_prefill(const uint16_t* q, int T, int q_pos0, const uint16_t* kpool,
                         const uint16_t* vpool, int block_size, const int32_t* block_table, int nh,
-                        int nkv, int hd, uint16_t* out, hipStream_t s);
+                        int nkv, int hd, uint16_t* out, hipStream_t s, int window = 0);
+// window W > 0: query p attends the keys p - W < k <= p.  q_pos0 + T <= W (the window covers every key) takes the
+// unwindowed kernel and launch geometry; otherwise the windowed variant (adjacent query blocks per work-group, the K/V ring
+// walks the work-group's band of tiles only)
 
 // k, v [T, nkv, hd] bf16 -> pool at slots [T] (-1 skips)
 int launch_kv_write(const uint16_t* k, const uint16_t* v, const int64_t* slots, int T, int nkv, int hd,
@@ -63,7 +68,7 @@ int launch_kv_write_f8(const uint16_t* k, const uint16_t* v, const int64_t* slot
 int launch_attn_decode_f8(const uint16_t* q, const uint8_t* kpool, const uint8_t* vpool, int block_size,
                           const int32_t* block_table, int MB, const int32_t* ctx_lens, int B, int nh, int nkv, int hd,
                           float k_scale, float v_scale, uint16_t* out, void* scratch, hipStream_t s, int rows_per_seq = 1,
-                          int num_blocks = 0);
+                          int num_blocks = 0, int window = 0);
 // launch_attn_prefill over the byte pool, read natively (attn_prefill_f8_kernel: codes widened once per work-group in
 // LDS, no bf16 copy in memory).  The same shape checks, plus block_size % 16 == 0 and positive scales; k_scale rides in
 // the score scale, v_scale multiplies the normalised output once.  No byte of a block the table names for keys
@@ -71,10 +76,13 @@ int launch_attn_decode_f8(const uint16_t* q, const uint8_t* kpool, const uint8_t
 int launch_attn_prefill_f8(const uint16_t* q, int T, int q_pos0, const uint8_t* kpool, const uint8_t* vpool,
                            int block_size, const int32_t* block_table, int nh, int nkv, int hd, float k_scale,
                            float v_scale, uint16_t* out, hipStream_t s);
+// (no windowed variant: a windowed context whose keys outgrow the window takes the staged path whatever the switch says)
 // One sequence's blocks 0 .. ceil(kv_len / block_size) - 1, in block-table order, widened to a bf16 pool
 // staged [2][nblk][nkv][block_size][hd] (element bf16_rne(float(code) * scale)) that launch_attn_prefill reads with an
 // identity block table.  pool: K bytes, then V bytes (num_blocks blocks each).
 int launch_kv_dequant_gather(const uint8_t* pool, int num_blocks, int block_size, const int32_t* block_table, int MB,
-                             int kv_len, int nkv, int hd, float k_scale, float v_scale, uint16_t* staged, hipStream_t s);
+                             int kv_len, int nkv, int hd, float k_scale, float v_scale, uint16_t* staged, hipStream_t s,
+                             int first_blk = 0);
+// first_blk > 0 (sliding window): only blocks first_blk .. are widened, into the places they have in the full staged pool
 
 }  // namespace mi

@@ -20,6 +20,9 @@
 // kernels have the same maps, query-block ownership, S^T / softmax / P.V step and epilogue and differ in how a tile
 // reaches its bf16 image in LDS: straight by DMA, or as codes that the work-group widens once.
 //
+// Sliding window (Mistral): the two token-generation kernels and attn_prefill2_kernel have a windowed instantiation (template
+// parameter SW) that walks only the K/V tiles the window touches; the unwindowed instantiations are the code they were.
+//
 // Also here: the standalone K/V writes into either pool and the FP8 -> bf16 staging gather.
 
 #include <type_traits>
@@ -79,13 +82,20 @@ typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 // ("the workgroup whose add came last, told by the value its add returned"; one work-group per
 // CU: the launch pads its LDS request to keep it so).  The merge itself runs in split order, so the
 // result does not depend on which work-group performs it.  The counter is left at 0 for the next launch.
-template <int HD, int NW, bool FINAL, bool MERGE = false>
+//
+// SW (sliding window W >= 1): column c attends the keys ctx_c - W <= tok < ctx_c.  The waves walk only the tiles the window
+// of the sequence touches: t_lo = max(0, min over the R rows of ctx_r - W) / 32 (for R = 1 that is max(0, ctx - W) / 32; with
+// R > 1 the row with the SHORTEST context has the lowest edge), dealt round-robin from t_lo on, so wave w of split s starts
+// at t_lo + s NW + w.  That tile depends on the context length: no early request.  A column whose first tile holds no live
+// key (its edge lies in a later tile than another column's) keeps m = -inf, l = 0 through sexp2's conventions.
+template <int HD, int NW, bool FINAL, bool MERGE = false, bool SW = false>
 __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ kpool, const uint16_t* __restrict__ vpool,
     int bs, const int32_t* __restrict__ block_table, int MB, const int32_t* __restrict__ ctx_lens,
     int nh, int nkv, int G, int NS, float* __restrict__ o_part, float* __restrict__ ml_part,
     uint16_t* __restrict__ out, float scale_log2e, unsigned int* __restrict__ tickets = nullptr, int R = 1,
-    int num_blocks = 0) {
+    int num_blocks = 0, int window = 0) {
+  static_assert(!(SW && MERGE), "the windowed form has no in-launch merge");
   // R > 1 (the target's pass of a speculation step): batch rows b R .. b R + R - 1 are the SAME sequence
   // at consecutive positions (one block-table row, context lengths growing by one).  Their query heads
   // sit side by side in the 16 MFMA columns (column = row-in-sequence * G + head, G R <= 16) and each
@@ -107,12 +117,19 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(
   int ctx = 0;                                  // the longest context of the sequence's rows bounds the tiles walked
   for (int r = 0; r < R; ++r) ctx = max(ctx, ctx_lens[b + r]);
   const int ctx_c = c < Gc ? ctx_lens[b + cr] : 0;   // what this lane's column may attend to
+  int t_lo = 0;                                 // SW: the first tile any row's window touches
+  if constexpr (SW) {
+    int lo = ctx;
+    for (int r = 0; r < R; ++r) lo = min(lo, ctx_lens[b + r]);
+    t_lo = max(lo - window, 0) / 32;
+  }
+  const int lo_c = SW ? ctx_c - window : 0;     // SW: the first key of this lane's column
   // Tiles are dealt round-robin: wave w of split s takes tiles s NW + w, + NS NW, ...  Which tile a wave STARTS
   // with therefore does not depend on the context length, so (num_blocks > 0) its first K/V request goes out
   // beside the load of the context length instead of behind it (one L2 round trip less on the way to the first
   // MFMA); what it fetched is masked by score, or never consumed when the tile lies beyond the context.
   const int nt = ceil_div(ctx, 32), stride = NS * NW;
-  const int t_first = split * NW + wave, t_end = nt;
+  const int t_first = t_lo + split * NW + wave, t_end = nt;
   uint16_t* Vw = Vs + wave * VT;
 
   u32x4_t kA[2 * KS], vA[NV], kB[2 * KS], vB[NV];
@@ -147,7 +164,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(
       vr[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(vpool + src));
     }
   };
-  if (num_blocks > 0) {
+  if (!SW && num_blocks > 0) {
     // speculative form of issue(): no use of the context length; table index and block id clamped into range
     const int tok0 = t_first * 32;
     size_t rowh[2];
@@ -219,6 +236,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(
       for (int i = 0; i < 4; ++i) {
         float sv = st[u][i] * scale_log2e;
         if (tok0 + 16 * u + 4 * g + i >= ctx_c) sv = -INFINITY;
+        if constexpr (SW) { if (tok0 + 16 * u + 4 * g + i < lo_c) sv = -INFINITY; }
         pv[4 * u + i] = sv;
         mx = fmaxf(mx, sv);
       }
@@ -397,7 +415,7 @@ static bool attn_merge_enabled() {
 template <int HD>
 static int launch_decode_t(const uint16_t* q, const uint16_t* kpool, const uint16_t* vpool, int bs,
                            const int32_t* bt, int MB, const int32_t* ctx, int B, int nh, int nkv,
-                           uint16_t* out, void* scratch, hipStream_t s, bool tickets_zeroed, int R, int num_blocks) {
+                           uint16_t* out, void* scratch, hipStream_t s, bool tickets_zeroed, int R, int num_blocks, int window) {
   const int G = nh / nkv, Bs = B / R, NS = attn_decode_splits(Bs, nkv);   // Bs sequences of R batch rows each
   // in-launch merge: needs every split's work-group resident on a CU of its own (grid <= CUs) and
   // the ticket counters at zero (the model keeps them so; the per-op entry cannot know)
@@ -410,6 +428,21 @@ static int launch_decode_t(const uint16_t* q, const uint16_t* kpool, const uint1
   const float scale_log2e = 1.4426950408889634f / sqrtf((float)HD);
   constexpr size_t lds8 = attn_decode_lds<HD, 8>(), lds4 = attn_decode_lds<HD, 4>();
   constexpr size_t kMergeLds = 96 * 1024;   // more than half a CU's LDS: one work-group per CU (see the kernel comment)
+  if (window > 0) {
+    // sliding window: the same split count, partial layout and combine; no in-launch merge, no early K/V request
+    MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_decode_kernel<HD, 8, true, false, true>), (int)lds8));
+    MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_decode_kernel<HD, 4, false, false, true>), (int)lds4));
+    if (NS == 1) {
+      hipLaunchKernelGGL((attn_decode_kernel<HD, 8, true, false, true>), dim3(1, nkv, Bs), dim3(512), lds8, s, q, kpool, vpool, bs,
+                         bt, MB, ctx, nh, nkv, G, 1, nullptr, nullptr, out, scale_log2e, nullptr, R, 0, window);
+    } else {
+      hipLaunchKernelGGL((attn_decode_kernel<HD, 4, false, false, true>), dim3(NS, nkv, Bs), dim3(256), lds4, s, q, kpool, vpool,
+                         bs, bt, MB, ctx, nh, nkv, G, NS, o_part, ml_part, nullptr, scale_log2e, nullptr, R, 0, window);
+      hipLaunchKernelGGL((attn_combine_kernel<HD>), dim3(nh, B), dim3(HD), 0, s, o_part, ml_part, NS, nh, out);
+    }
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+  }
   {
     int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(attn_decode_kernel<HD, 8, true>), (int)lds8);
     if (rc == MI_OK) rc = ensure_dynamic_lds(reinterpret_cast<const void*>(attn_decode_kernel<HD, 4, false>), (int)lds4);
@@ -438,14 +471,16 @@ static int launch_decode_t(const uint16_t* q, const uint16_t* kpool, const uint1
 int launch_attn_decode(const uint16_t* q, const uint16_t* kpool, const uint16_t* vpool, int block_size,
                        const int32_t* block_table, int MB, const int32_t* ctx_lens, int B, int nh,
                        int nkv, int hd, uint16_t* out, void* scratch, hipStream_t s, bool tickets_zeroed, int rows_per_seq,
-                       int num_blocks) {
+                       int num_blocks, int window) {
   MI_CHECK(hd == 64 || hd == 128, "attention: head_dim must be 64 or 128");
+  MI_CHECK(window >= 0, "attention: the sliding window must be >= 0 (0 = none)");
+  if ((long)MB * block_size <= window) window = 0;   // no row of this table can hold a key outside the window: the unwindowed launch
   MI_CHECK(rows_per_seq >= 1 && B % rows_per_seq == 0 && (nh / nkv) * rows_per_seq <= 16,
            "attention: rows_per_seq must divide the batch and q heads per kv head x rows_per_seq must be <= 16");
   MI_CHECK(nh % nkv == 0 && nh / nkv <= 16, "attention: q heads per kv head must be 1..16");
   MI_CHECK(block_size % 16 == 0, "attention: block_size must be a multiple of 16");
-  if (hd == 128) return launch_decode_t<128>(q, kpool, vpool, block_size, block_table, MB, ctx_lens, B, nh, nkv, out, scratch, s, tickets_zeroed, rows_per_seq, num_blocks);
-  return launch_decode_t<64>(q, kpool, vpool, block_size, block_table, MB, ctx_lens, B, nh, nkv, out, scratch, s, tickets_zeroed, rows_per_seq, num_blocks);
+  if (hd == 128) return launch_decode_t<128>(q, kpool, vpool, block_size, block_table, MB, ctx_lens, B, nh, nkv, out, scratch, s, tickets_zeroed, rows_per_seq, num_blocks, window);
+  return launch_decode_t<64>(q, kpool, vpool, block_size, block_table, MB, ctx_lens, B, nh, nkv, out, scratch, s, tickets_zeroed, rows_per_seq, num_blocks, window);
 }
 
 // =====================================================================================
@@ -475,12 +510,14 @@ int launch_attn_decode(const uint16_t* q, const uint16_t* kpool, const uint16_t*
 // never holds one; a caller of mi_op_paged_attn_decode_f8 that owns its pool must keep that promise.
 typedef __attribute__((ext_vector_type(2))) int i32x2_t;
 
-template <int HD, int NW, bool FINAL>
+// SW: attn_decode_kernel's sliding window over 64-token tiles (t_lo = max(0, min ctx_r - W) / 64); a 32-token half that lies
+// wholly below every row's window is skipped like one beyond the context.
+template <int HD, int NW, bool FINAL, bool SW = false>
 __global__ __launch_bounds__(NW * 64) void attn_decode_f8_kernel(
     const uint16_t* __restrict__ q, const uint8_t* __restrict__ kpool, const uint8_t* __restrict__ vpool,
     int bs, const int32_t* __restrict__ block_table, int MB, const int32_t* __restrict__ ctx_lens,
     int nh, int nkv, int G, int NS, float* __restrict__ o_part, float* __restrict__ ml_part,
-    uint16_t* __restrict__ out, float score_scale, float v_scale, int R, int num_blocks) {
+    uint16_t* __restrict__ out, float score_scale, float v_scale, int R, int num_blocks, int window = 0) {
   constexpr int TT = 64;            // tokens per tile
   constexpr int KPB = HD + 16;      // LDS row pitch (bytes)
   constexpr int CPR = HD / 16;      // 16-byte chunks per row
@@ -501,8 +538,15 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_f8_kernel(
   int ctx = 0;
   for (int r = 0; r < R; ++r) ctx = max(ctx, ctx_lens[b + r]);
   const int ctx_c = c < Gc ? ctx_lens[b + cr] : 0;
+  int key_lo = 0;                               // SW: the first key any row's window holds
+  if constexpr (SW) {
+    int lo = ctx;
+    for (int r = 0; r < R; ++r) lo = min(lo, ctx_lens[b + r]);
+    key_lo = max(lo - window, 0);
+  }
+  const int lo_c = SW ? ctx_c - window : 0;     // SW: the first key of this lane's column
   const int nt = ceil_div(ctx, TT), stride = NS * NW;
-  const int t_first = split * NW + wave, t_end = nt;
+  const int t_first = key_lo / TT + split * NW + wave, t_end = nt;
   unsigned char* Vw = dsm + (size_t)wave * VT;
 
   u32x4_t kA[NK], vA[NV], kB[NK], vB[NV];
@@ -541,7 +585,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_f8_kernel(
       vr[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(vpool + src));
     }
   };
-  issue(kA, vA, t_first, num_blocks > 0);
+  issue(kA, vA, t_first, !SW && num_blocks > 0);
 
   // q fragment (j, e) of lane (g, c): head column c, dims 64 j + 16 g + 8 e .. + 7
   u32x4_t qf[KS];
@@ -569,6 +613,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_f8_kernel(
     for (int h = 0; h < 2; ++h) {
       const int tok0 = tt * TT + 32 * h;
       if (tok0 >= ctx) break;         // wave-uniform: the whole half lies beyond the context
+      if constexpr (SW) { if (tok0 + 32 <= key_lo) continue; }   // ... or below every row's window
       f32x4_t st[2];
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
@@ -592,6 +637,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_f8_kernel(
         for (int i = 0; i < 4; ++i) {
           float sv = st[u][i] * score_scale;
           if (tok0 + 16 * u + 4 * g + i >= ctx_c) sv = -INFINITY;
+          if constexpr (SW) { if (tok0 + 16 * u + 4 * g + i < lo_c) sv = -INFINITY; }
           pv[4 * u + i] = sv;
           mx = fmaxf(mx, sv);
         }
@@ -673,7 +719,7 @@ constexpr size_t attn_decode_f8_lds() { return (size_t)NW * 64 * (HD + 16) + (si
 template <int HD>
 static int launch_decode_f8_t(const uint16_t* q, const uint8_t* kpool, const uint8_t* vpool, int bs, const int32_t* bt,
                               int MB, const int32_t* ctx, int B, int nh, int nkv, float k_scale, float v_scale,
-                              uint16_t* out, void* scratch, hipStream_t s, int R, int num_blocks) {
+                              uint16_t* out, void* scratch, hipStream_t s, int R, int num_blocks, int window) {
   const int G = nh / nkv, Bs = B / R, NS = attn_decode_splits(Bs, nkv);   // Bs sequences of R batch rows each
   float* ml_part = reinterpret_cast<float*>(reinterpret_cast<unsigned int*>(scratch) + kAttnTickets);
   float* o_part = ml_part + (size_t)B * nh * kAttnMaxSplits * 2;
@@ -681,6 +727,20 @@ static int launch_decode_f8_t(const uint16_t* q, const uint8_t* kpool, const uin
   constexpr size_t lds8 = attn_decode_f8_lds<HD, 8>(), lds4 = attn_decode_f8_lds<HD, 4>();
   MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_decode_f8_kernel<HD, 8, true>), (int)lds8));
   MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_decode_f8_kernel<HD, 4, false>), (int)lds4));
+  if (window > 0) {
+    MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_decode_f8_kernel<HD, 8, true, true>), (int)lds8));
+    MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_decode_f8_kernel<HD, 4, false, true>), (int)lds4));
+    if (NS == 1) {
+      hipLaunchKernelGGL((attn_decode_f8_kernel<HD, 8, true, true>), dim3(1, nkv, Bs), dim3(512), lds8, s, q, kpool, vpool, bs, bt,
+                         MB, ctx, nh, nkv, G, 1, nullptr, nullptr, out, score_scale, v_scale, R, 0, window);
+    } else {
+      hipLaunchKernelGGL((attn_decode_f8_kernel<HD, 4, false, true>), dim3(NS, nkv, Bs), dim3(256), lds4, s, q, kpool, vpool, bs, bt,
+                         MB, ctx, nh, nkv, G, NS, o_part, ml_part, nullptr, score_scale, v_scale, R, 0, window);
+      hipLaunchKernelGGL((attn_combine_kernel<HD>), dim3(nh, B), dim3(HD), 0, s, o_part, ml_part, NS, nh, out);
+    }
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+  }
   if (NS == 1) {
     hipLaunchKernelGGL((attn_decode_f8_kernel<HD, 8, true>), dim3(1, nkv, Bs), dim3(512), lds8, s, q, kpool, vpool, bs, bt,
                        MB, ctx, nh, nkv, G, 1, nullptr, nullptr, out, score_scale, v_scale, R, num_blocks);
@@ -696,15 +756,17 @@ static int launch_decode_f8_t(const uint16_t* q, const uint8_t* kpool, const uin
 int launch_attn_decode_f8(const uint16_t* q, const uint8_t* kpool, const uint8_t* vpool, int block_size,
                           const int32_t* block_table, int MB, const int32_t* ctx_lens, int B, int nh, int nkv, int hd,
                           float k_scale, float v_scale, uint16_t* out, void* scratch, hipStream_t s, int rows_per_seq,
-                          int num_blocks) {
+                          int num_blocks, int window) {
   MI_CHECK(hd == 64 || hd == 128, "attention: head_dim must be 64 or 128");
+  MI_CHECK(window >= 0, "attention: the sliding window must be >= 0 (0 = none)");
+  if ((long)MB * block_size <= window) window = 0;   // no row of this table can hold a key outside the window: the unwindowed launch
   MI_CHECK(rows_per_seq >= 1 && B % rows_per_seq == 0 && (nh / nkv) * rows_per_seq <= 16,
            "attention: rows_per_seq must divide the batch and q heads per kv head x rows_per_seq must be <= 16");
   MI_CHECK(nh % nkv == 0 && nh / nkv <= 16, "attention: q heads per kv head must be 1..16");
   MI_CHECK(block_size % 16 == 0, "attention: block_size must be a multiple of 16");
   MI_CHECK(MB >= 1 && k_scale > 0.f && v_scale > 0.f, "attention: the block table width and the FP8 KV scales must be positive");
-  if (hd == 128) return launch_decode_f8_t<128>(q, kpool, vpool, block_size, block_table, MB, ctx_lens, B, nh, nkv, k_scale, v_scale, out, scratch, s, rows_per_seq, num_blocks);
-  return launch_decode_f8_t<64>(q, kpool, vpool, block_size, block_table, MB, ctx_lens, B, nh, nkv, k_scale, v_scale, out, scratch, s, rows_per_seq, num_blocks);
+  if (hd == 128) return launch_decode_f8_t<128>(q, kpool, vpool, block_size, block_table, MB, ctx_lens, B, nh, nkv, k_scale, v_scale, out, scratch, s, rows_per_seq, num_blocks, window);
+  return launch_decode_f8_t<64>(q, kpool, vpool, block_size, block_table, MB, ctx_lens, B, nh, nkv, k_scale, v_scale, out, scratch, s, rows_per_seq, num_blocks, window);
 }
 
 // =====================================================================================
@@ -767,11 +829,22 @@ constexpr int attn_prefill_lds() { return PrefillTile<HD>::NSTAGE * PrefillTile<
 template <int HD>   // the code ring and a double-buffered image
 constexpr int attn_prefill_f8_lds() { return PrefillTile<HD>::NSTAGE * PrefillTile<HD>::CSTAGE + 2 * PrefillTile<HD>::ISTAGE; }
 
-template <int HD, int NW>
+//
+// SW (sliding window W >= 1, launched only when q_pos0 + T > W): query p attends the keys p - W < k <= p, so the work of a
+// 32-query block is a BAND of about (W + 95) / 64 key tiles whatever its index, and the bands of a heavy and a light block
+// do not overlap: a pair sharing a ring would stream tiles only one of them wants.  A work-group therefore owns the QB =
+// NW / Gp ADJACENT blocks blockIdx.x QB .. + QB - 1 (same head slots), one pass, and its ring walks the union of their
+// bands: tiles t_lo_wg = max(0, q_pos0 + q0_first - W + 1) / 64 .. the last tile of its last block.  Every wave issues
+// its share of every tile's DMA pieces and passes every barrier, but runs MFMAs and softmax only on the tiles of its own
+// band.  The lower-edge mask (key < qpos - W + 1) is applied on tiles that straddle the edge of one of the wave's queries,
+// the causal mask on diagonal tiles as before.  A row can meet a tile with no live key before its first live one (its edge
+// lies further right than its block's first): its running maximum stays -inf and the exponent takes 0 in its place, so
+// p = exp2(-inf) = 0 and neither l nor O moves.
+template <int HD, int NW, bool SW = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_prefill2_kernel(
     const uint16_t* __restrict__ q, int T, int q_pos0, const uint16_t* __restrict__ kpool,
     const uint16_t* __restrict__ vpool, int bs, int bs_shift, const int32_t* __restrict__ block_table, int nh, int nkv,
-    int G, int Gp, int nblk, uint16_t* __restrict__ out, float scale_log2e) {
+    int G, int Gp, int nblk, uint16_t* __restrict__ out, float scale_log2e, int window = 0) {
   using P = PrefillTile<HD>;
   constexpr int TK = P::TK, ROWB = P::ROWB, KBYTES = P::KIMG, STAGE = P::ISTAGE, NSTAGE = P::NSTAGE;
   constexpr int CPR = HD / 8;                  // 16-byte chunks per row
@@ -819,12 +892,16 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
       vaddr[db][u] = key * ROWB + ((chunk ^ kv_swz<HD>(key)) * 16) + 8 * (pc & 1);
     }
 
-  const int passes = QB == 1 ? 2 : 1;
+  const int passes = (!SW && QB == 1) ? 2 : 1;
   for (int pass = 0; pass < passes; ++pass) {
     // ---- which query block this wave owns --------------------------------------------------------
     int blk_q, pair;
     bool blk_ok;
-    if (QB == 1) {                       // one block at a time: the heavy one of pair blockIdx.x, then the light one
+    if constexpr (SW) {                  // adjacent blocks
+      pair = 0;
+      blk_q = (int)blockIdx.x * QB + slot;
+      blk_ok = blk_q < nblk;
+    } else if (QB == 1) {                // one block at a time: the heavy one of pair blockIdx.x, then the light one
       pair = blockIdx.x;
       blk_q = pass == 0 ? nblk - 1 - pair : pair;
       blk_ok = pair < npair && !(pass == 1 && pair == nblk - 1 - pair);
@@ -840,12 +917,17 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const int nt_wave = active ? p_last / TK + 1 : 0;
     int wg_pair0 = QB == 1 ? (int)blockIdx.x : (int)blockIdx.x * (QB >> 1);
     int wg_blk = QB == 1 ? (pass == 0 ? nblk - 1 - wg_pair0 : wg_pair0) : nblk - 1 - wg_pair0;   // heaviest block of the work-group
+    if constexpr (SW) wg_blk = (int)blockIdx.x * QB + QB - 1;                                    // SW: its last block
     wg_blk = max(min(wg_blk, nblk - 1), 0);
     const int nt = (q_pos0 + min(wg_blk * 32 + 31, T - 1)) / TK + 1;
+    // SW: first tile of the work-group's ring and of this wave's band; first key of this lane's query (below)
+    const int t0 = SW ? max(q_pos0 + (int)blockIdx.x * QB * 32 - window + 1, 0) / TK : 0;
+    const int t_lo_wave = SW ? max(p_first - window + 1, 0) / TK : 0;
 
     // ---- Q fragments (B operand of S^T): Q[q0 + qq][16 ks + 8 h ..] ---------------------------------
     const int qi = min(q0 + qq, T - 1);
     const int qpos = q_pos0 + qi;
+    const int klo = SW ? qpos - window + 1 : 0;
     u32x4_t qf[KSTEPS];
 #pragma unroll
     for (int ks = 0; ks < KSTEPS; ++ks)
@@ -883,16 +965,16 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     };
 
     int st_issue = 0, st_read = 0;
-    fetch_ids(0);
+    fetch_ids(t0);
     issue(0);
-    if (nt > 1) { fetch_ids(1); issue(1); }
-    fetch_ids(2);
+    if (nt > t0 + 1) { fetch_ids(t0 + 1); issue(1); }
+    fetch_ids(t0 + 2);
     st_issue = 2;
     // hipcc waits for a plain load at its first use -- inside the tile loop, as vmcnt(0) on every iteration, which would drain
     // the two tiles in flight each time.  Taking the Q fragments through an empty asm here puts that wait in front of the loop.
 #pragma unroll
     for (int ks = 0; ks < KSTEPS; ++ks) asm volatile("" : "+v"(qf[ks]));
-    for (int t = 0; t < nt; ++t) {
+    for (int t = t0; t < nt; ++t) {
       if (t + 1 < nt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT) : "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();            // every wave's pieces of tile t are in; everyone is done reading tile t - 1
@@ -905,6 +987,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
       const unsigned char* Vst = Kst + KBYTES;
       st_read = st_read == NSTAGE - 1 ? 0 : st_read + 1;
       if (t >= nt_wave) continue;                // wave-uniform: the tile lies in this block's future (or the slot is idle)
+      if constexpr (SW) { if (t < t_lo_wave) continue; }   // ... or wholly below the window of its first query
 
       // ---- S^T = K . Q^T : two 32-key blocks.  The K fragments of a block are requested one block ahead of the MFMAs
       // that take them (8 reads in flight; hipcc left to itself issues read -> wait -> MFMA one at a time) ----
@@ -941,6 +1024,15 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
           for (int r = 0; r < 16; ++r)
             if (t * TK + 32 * b + (r & 3) + 8 * (r >> 2) + 4 * h > qpos) sc[b][r] = -INFINITY;
       }
+      if constexpr (SW) {
+        if (t * TK < p_last - window + 1) {      // the tile straddles the lower edge of one of the wave's queries
+#pragma unroll
+          for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+              if (t * TK + 32 * b + (r & 3) + 8 * (r >> 2) + 4 * h < klo) sc[b][r] = -INFINITY;
+        }
+      }
       float mx = sc[0][0];
 #pragma unroll
       for (int b = 0; b < 2; ++b)
@@ -950,7 +1042,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         const f32x2_t sw = swap32_pair(mx);
         mx = fmaxf(sw[0], sw[1]);
       }
-      const float ms = mx * scale_log2e;         // key 0 is visible to every query: finite from the first tile on
+      const float ms = mx * scale_log2e;         // key 0 is visible to every query: finite from the first tile on (SW: -inf until the row's first live tile)
       const bool moved = ms > m_used + kDeferLog2;
       if (__any(moved)) {
         const float mn = moved ? ms : m_used;
@@ -982,12 +1074,14 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
       MI_VREAD(0); MI_VREAD(1); MI_VREAD(2); MI_VREAD(3);
       static_assert(kVAhead == 4, "the prefetch above is written out for 4");
       bf16x8_t pb[4];
+      // SW: a row with no live key so far has m_used = -inf and only masked scores: 0 in its place keeps -inf - m from being NaN
+      const float m_exp = (SW && m_used == -INFINITY) ? 0.f : m_used;
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         float pv[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          pv[r] = fexp2(fmaf(sc[b][r], scale_log2e, -m_used));   // masked: exp2(-inf) = 0
+          pv[r] = fexp2(fmaf(sc[b][r], scale_log2e, -m_exp));   // masked: exp2(-inf) = 0
           lsum += pv[r];
         }
 #pragma unroll
@@ -1392,10 +1486,37 @@ static int prefill_launch_geometry(int T, int q_pos0, int block_size, int nh, in
   return MI_OK;
 }
 
+// Sliding window: 8 waves = (8 / Gp) ADJACENT query blocks x Gp heads, grid ceil(nblk / (8 / Gp)) x nkv.
+// Blocks per work-group: a block's band is (W + 95) / 64 tiles wherever it lies, so every work-group carries the same load
+// and nothing is gained by pairing; what the count decides is how much of the ring a wave sits out.  With QB adjacent
+// blocks the ring walks (W + 32 QB + 63) / 64 tiles and a wave multiplies (W + 95) / 64 of them: at QB = 2 (4 q heads per
+// kv head, the common GQA shape) one tile in 66 at W 4096 is skipped, at QB = 8 (MHA) 4 in 69 -- a skipped tile costs a
+// wave its DMA share and a barrier, no MFMA.  Fewer blocks than 8 / Gp would leave waves of the work-group idle for the
+// whole launch (the head slots are fixed by Gp), more would need a second pass over a ring that no longer overlaps: so
+// 8 / Gp it is, the slot layout of the unwindowed kernel.
+static int prefill_sw_launch_geometry(int T, int q_pos0, int block_size, int nh, int nkv, int hd, PrefillLaunch* g) {
+  MI_TRY_A(prefill_launch_geometry(T, q_pos0, block_size, nh, nkv, hd, g));
+  g->grid = dim3(ceil_div(g->nblk, 8 / g->Gp), nkv);
+  return MI_OK;
+}
+
 int launch_attn_prefill(const uint16_t* q, int T, int q_pos0, const uint16_t* kpool, const uint16_t* vpool,
                         int block_size, const int32_t* block_table, int nh, int nkv, int hd, uint16_t* out,
-                        hipStream_t s) {
+                        hipStream_t s, int window) {
+  MI_CHECK(window >= 0, "attention: the sliding window must be >= 0 (0 = none)");
   PrefillLaunch g;
+  if (window > 0 && q_pos0 + T > window) {   // else the window covers every key: the unwindowed kernel and geometry
+    MI_TRY_A(prefill_sw_launch_geometry(T, q_pos0, block_size, nh, nkv, hd, &g));
+    auto launch_sw = [&](auto hd_c) -> int {
+      constexpr int HD = decltype(hd_c)::value, lds = attn_prefill_lds<HD>();
+      MI_TRY_A(ensure_dynamic_lds(reinterpret_cast<const void*>(attn_prefill2_kernel<HD, 8, true>), lds));
+      hipLaunchKernelGGL((attn_prefill2_kernel<HD, 8, true>), g.grid, dim3(512), lds, s, q, T, q_pos0, kpool, vpool, block_size,
+                         g.bs_shift, block_table, nh, nkv, g.G, g.Gp, g.nblk, out, g.scale_log2e, window);
+      MI_HIP(hipGetLastError());
+      return MI_OK;
+    };
+    return hd == 128 ? launch_sw(std::integral_constant<int, 128>{}) : launch_sw(std::integral_constant<int, 64>{});
+  }
   MI_TRY_A(prefill_launch_geometry(T, q_pos0, block_size, nh, nkv, hd, &g));
   auto launch = [&](auto hd_c) -> int {
     constexpr int HD = decltype(hd_c)::value, lds = attn_prefill_lds<HD>();
@@ -1587,12 +1708,17 @@ __global__ __launch_bounds__(256) void kv_dequant_gather_kernel(const uint8_t* _
 }
 
 int launch_kv_dequant_gather(const uint8_t* pool, int num_blocks, int block_size, const int32_t* block_table, int MB,
-                             int kv_len, int nkv, int hd, float k_scale, float v_scale, uint16_t* staged, hipStream_t s) {
+                             int kv_len, int nkv, int hd, float k_scale, float v_scale, uint16_t* staged, hipStream_t s,
+                             int first_blk) {
   MI_CHECK(hd % 16 == 0 && num_blocks >= 1 && block_size >= 1 && nkv >= 1, "kv_dequant_gather: bad pool geometry");
   MI_CHECK(kv_len >= 1 && ceil_div(kv_len, block_size) <= MB, "kv_dequant_gather: block_table narrower than the context");
   const int nblk = ceil_div(kv_len, block_size), blk_bytes = nkv * block_size * hd;
-  hipLaunchKernelGGL(kv_dequant_gather_kernel, dim3(ceil_div(blk_bytes / 16, 256), nblk, 2), dim3(256), 0, s, pool,
-                     (size_t)num_blocks * blk_bytes, num_blocks, blk_bytes, block_table, nblk, k_scale, v_scale, staged);
+  MI_CHECK(first_blk >= 0 && first_blk < nblk, "kv_dequant_gather: first block outside the context");
+  // blocks first_blk .. nblk - 1 keep their place in the staged pool: the kernel sees the table and the staged pool from
+  // first_blk on, with nblk still the stride between the K and the V part
+  hipLaunchKernelGGL(kv_dequant_gather_kernel, dim3(ceil_div(blk_bytes / 16, 256), nblk - first_blk, 2), dim3(256), 0, s, pool,
+                     (size_t)num_blocks * blk_bytes, num_blocks, blk_bytes, block_table + first_blk, nblk, k_scale, v_scale,
+                     staged + (size_t)first_blk * blk_bytes);
   MI_HIP(hipGetLastError());
   return MI_OK;
 }

@@ -263,15 +263,20 @@ int run_layers(mi_ctx* c, int rows, bool decode, int B, int MB, int q_pos0, int 
     uint16_t* vpool = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(kpool) + c->kv_half * c->kv_esz());
     const uint8_t *kpool8 = reinterpret_cast<const uint8_t*>(kpool), *vpool8 = reinterpret_cast<const uint8_t*>(vpool);
     const float ksc = c->k_scale[l], vsc = c->v_scale[l];
+    const int win = c->window;   // sliding window of this context (0: none); every attention launch below takes it
     // FP8 KV, context encoding: stage the sequence's keys 0 .. kv_len - 1 as bf16, then the bf16 kernel with the identity
     // table; the A/B switch runs the native kernel on the byte pool with the request's own table row instead
     auto prefill_f8 = [&](const uint16_t* qp, int n, int pos0, const int32_t* bt, uint16_t* outp) -> int {
-      if (attn_prefill_f8_native())
+      const bool windowed = win > 0 && pos0 + n > win;   // the native kernel has no windowed variant: staged path whatever the switch says
+      if (attn_prefill_f8_native() && !windowed)
         return launch_attn_prefill_f8(qp, n, pos0, kpool8, vpool8, k.block_size, bt, c->nh_l, c->nkv_l, c->hd, ksc, vsc, outp, s);
       const int nblk = ceil_div(pos0 + n, k.block_size);
-      MI_TRY(launch_kv_dequant_gather(kpool8, k.num_blocks, k.block_size, bt, MB, pos0 + n, c->nkv_l, c->hd, ksc, vsc, c->kv_stage, s));
+      // windowed: no query reaches below key pos0 - win + 1, and the kernel's first 64-key tile is the one that holds it.  The
+      // blocks from that TILE's first key on are staged at their absolute index (P = 0 does not silence a stale NaN in V).
+      const int blk0 = windowed ? (std::max(pos0 - win + 1, 0) / 64 * 64) / k.block_size : 0;
+      MI_TRY(launch_kv_dequant_gather(kpool8, k.num_blocks, k.block_size, bt, MB, pos0 + n, c->nkv_l, c->hd, ksc, vsc, c->kv_stage, s, blk0));
       return launch_attn_prefill(qp, n, pos0, c->kv_stage, c->kv_stage + (size_t)nblk * c->nkv_l * k.block_size * c->hd,
-                                 k.block_size, c->d_ident, c->nh_l, c->nkv_l, c->hd, outp, s);
+                                 k.block_size, c->d_ident, c->nh_l, c->nkv_l, c->hd, outp, s, win);
     };
     {  // norm -> QKV -> RoPE -> q / KV pool
       ProArgs p{};
@@ -305,11 +310,11 @@ int run_layers(mi_ctx* c, int rows, bool decode, int B, int MB, int q_pos0, int 
       Scope sc(c, MI_K_ATTN_DECODE);
       if (f8) MI_TRY(launch_attn_decode_f8(c->qbuf, kpool8, vpool8, k.block_size, c->d_bt, MB, c->d_ctx, B, c->nh_l, c->nkv_l, c->hd,
                                            ksc, vsc, c->attn_out, c->attn_scratch, s, c->attn_rows_per_seq,
-                                           attn_early_kv() ? k.num_blocks : 0));
+                                           attn_early_kv() ? k.num_blocks : 0, win));
       else
       MI_TRY(launch_attn_decode(c->qbuf, kpool, vpool, k.block_size, c->d_bt, MB, c->d_ctx, B, c->nh_l,
                                 c->nkv_l, c->hd, c->attn_out, c->attn_scratch, s, /*tickets_zeroed=*/true,
-                                c->attn_rows_per_seq, attn_early_kv() ? k.num_blocks : 0));
+                                c->attn_rows_per_seq, attn_early_kv() ? k.num_blocks : 0, win));
     } else if (segs) {
       Scope sc(c, MI_K_ATTN_PREFILL);
       static const bool batch_decodes = [] { const char* v = getenv("MI355X_RAGGED_DECODE_ATTN"); return !v || v[0] != '0'; }();
@@ -322,12 +327,12 @@ int run_layers(mi_ctx* c, int rows, bool decode, int B, int MB, int q_pos0, int 
           if (f8) MI_TRY(launch_attn_decode_f8(c->qbuf + (size_t)segs[i].row0 * c->q_dim, kpool8, vpool8, k.block_size,
                                                c->d_bt + (size_t)i * MB, MB, c->d_seg_ctx + i, j - i, c->nh_l, c->nkv_l, c->hd, ksc, vsc,
                                                c->attn_out + (size_t)segs[i].row0 * c->q_dim, c->attn_scratch, s, 1,
-                                               attn_early_kv() ? k.num_blocks : 0));
+                                               attn_early_kv() ? k.num_blocks : 0, win));
           else
           MI_TRY(launch_attn_decode(c->qbuf + (size_t)segs[i].row0 * c->q_dim, kpool, vpool, k.block_size,
                                     c->d_bt + (size_t)i * MB, MB, c->d_seg_ctx + i, j - i, c->nh_l, c->nkv_l, c->hd,
                                     c->attn_out + (size_t)segs[i].row0 * c->q_dim, c->attn_scratch, s, false, 1,
-                                    attn_early_kv() ? k.num_blocks : 0));
+                                    attn_early_kv() ? k.num_blocks : 0, win));
           i = j;
           continue;
         }
@@ -336,7 +341,7 @@ int run_layers(mi_ctx* c, int rows, bool decode, int B, int MB, int q_pos0, int 
         else
         MI_TRY(launch_attn_prefill(c->qbuf + (size_t)segs[i].row0 * c->q_dim, segs[i].n, segs[i].pos0, kpool, vpool,
                                    k.block_size, c->d_bt + (size_t)i * MB, c->nh_l, c->nkv_l, c->hd,
-                                   c->attn_out + (size_t)segs[i].row0 * c->q_dim, s));
+                                   c->attn_out + (size_t)segs[i].row0 * c->q_dim, s, win));
         ++i;
       }
     } else {
@@ -344,7 +349,7 @@ int run_layers(mi_ctx* c, int rows, bool decode, int B, int MB, int q_pos0, int 
       if (f8) MI_TRY(prefill_f8(c->qbuf, rows, q_pos0, c->d_bt, c->attn_out));
       else
       MI_TRY(launch_attn_prefill(c->qbuf, rows, q_pos0, kpool, vpool, k.block_size, c->d_bt, c->nh_l,
-                                 c->nkv_l, c->hd, c->attn_out, s));
+                                 c->nkv_l, c->hd, c->attn_out, s, win));
     }
     const bool tp = c->collective();  // a communicator (even of one rank) selects the collective path
     {  // O projection.  TP = 1: straight into the residual stream (resid' = resid + y);
@@ -635,7 +640,7 @@ int capture_or_launch_decode(mi_ctx* c, int B, int MB) {
 extern "C" {
 
 const char* mi_last_error(void) { return mi::g_err.c_str(); }
-int mi_version(void) { return 7; }   // 7: + qk_norm, mi_op_qk_norm_rope_kv (Qwen3); 6: + mi_op_paged_attn_prefill_f8; 5: + kv_cache_dtype, mi_op_kv_write_f8 / mi_op_paged_attn_decode_f8 / mi_op_kv_dequant_gather; 4: + mi_tp_plan, mi_tp_info; 3: + in-process tensor parallelism (tp_rank = MI_TP_ALL_RANKS, tp_device_ids, tp_transport)
+int mi_version(void) { return 8; }   // 8: + sliding_window, mi_op_paged_attn_decode_sw / mi_op_paged_attn_prefill_sw (Mistral); 7: + qk_norm, mi_op_qk_norm_rope_kv (Qwen3); 6: + mi_op_paged_attn_prefill_f8; 5: + kv_cache_dtype, mi_op_kv_write_f8 / mi_op_paged_attn_decode_f8 / mi_op_kv_dequant_gather; 4: + mi_tp_plan, mi_tp_info; 3: + in-process tensor parallelism (tp_rank = MI_TP_ALL_RANKS, tp_device_ids, tp_transport)
 
 int mi_tp_plan(const mi_model_config* cfg, int32_t rank, mi_tp_plan_t* out) {
   MI_CHECK(cfg && out, "null argument");
@@ -703,6 +708,7 @@ int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out) {
   MI_CHECK(k.quant_type == MI_Q_PER_TENSOR_SYMMETRIC || k.quant_type == MI_Q_PER_CHANNEL_SYMMETRIC, "quant_type");
   MI_CHECK(k.kv_cache_dtype == MI_KV_BF16 || k.kv_cache_dtype == MI_KV_F8E4M3, "kv_cache_dtype");
   MI_CHECK(k.qk_norm == 0 || k.qk_norm == 1, "qk_norm");
+  MI_CHECK(k.sliding_window >= 0, "sliding_window must be >= 0 (0 = none)");
   int ndev = 0;
   MI_HIP(hipGetDeviceCount(&ndev));
   MI_CHECK(ndev > 0, "no HIP device: this library has no CPU fallback");
@@ -715,6 +721,7 @@ int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out) {
   MI_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   c->H = k.hidden_size;
   c->hd = k.head_dim;
+  c->window = k.sliding_window < k.max_model_len ? k.sliding_window : 0;   // a window no sequence can outgrow is no window
   // Head sharding.  kv heads >= ranks: whole kv groups per rank.  Fewer kv heads than ranks: every kv head is
   // replicated on R = T / nkv ranks and its G q heads are dealt to them ceil(G / R) at a time; where R does not
   // divide G the last rank(s) of a group hold ZERO-WEIGHT padding heads (q rows, q bias and o_proj columns zero:
@@ -1933,6 +1940,36 @@ int mi_op_paged_attn_prefill(const void* q, int32_t T, int32_t q_pos0, const voi
   const uint16_t* vp = kp + (size_t)num_blocks * nkv * block_size * hd;
   return launch_attn_prefill(reinterpret_cast<const uint16_t*>(q), T, q_pos0, kp, vp, block_size, block_table, nh, nkv,
                              hd, reinterpret_cast<uint16_t*>(out), (hipStream_t)stream);
+}
+int mi_op_paged_attn_decode_sw(const void* q, const void* pool, int32_t num_blocks, int32_t block_size,
+                               const int32_t* block_table, int32_t MB, const int32_t* ctx_lens, int32_t B, int32_t nh, int32_t nkv,
+                               int32_t hd, int32_t kv_dtype, float k_scale, float v_scale, int32_t window, void* out,
+                               void* scratch, void* stream) {
+  MI_CHECK(q && pool && block_table && ctx_lens && out && scratch, "null argument");
+  MI_CHECK(kv_dtype == MI_KV_BF16 || kv_dtype == MI_KV_F8E4M3, "kv_dtype");
+  MI_CHECK(num_blocks >= 1 && block_size >= 1 && nkv >= 1 && MB >= 1, "attention: empty pool");
+  MI_CHECK(window >= 0, "attention: the sliding window must be >= 0 (0 = none)");
+  const size_t half = (size_t)num_blocks * nkv * block_size * hd;   // elements of the K pool
+  if (kv_dtype == MI_KV_F8E4M3) {
+    const uint8_t* kp = reinterpret_cast<const uint8_t*>(pool);
+    return launch_attn_decode_f8(reinterpret_cast<const uint16_t*>(q), kp, kp + half, block_size, block_table, MB, ctx_lens, B, nh,
+                                 nkv, hd, k_scale, v_scale, reinterpret_cast<uint16_t*>(out), scratch, (hipStream_t)stream,
+                                 /*rows_per_seq=*/1, num_blocks, window);
+  }
+  const uint16_t* kp = reinterpret_cast<const uint16_t*>(pool);
+  return launch_attn_decode(reinterpret_cast<const uint16_t*>(q), kp, kp + half, block_size, block_table, MB, ctx_lens, B, nh,
+                            nkv, hd, reinterpret_cast<uint16_t*>(out), scratch, (hipStream_t)stream, false, 1, 0, window);
+}
+int mi_op_paged_attn_prefill_sw(const void* q, int32_t T, int32_t q_pos0, const void* pool, int32_t num_blocks,
+                                int32_t block_size, const int32_t* block_table, int32_t MB, int32_t nh, int32_t nkv,
+                                int32_t hd, int32_t window, void* out, void* stream) {
+  MI_CHECK(q && pool && block_table && out, "null argument");
+  MI_CHECK(num_blocks >= 1 && block_size >= 1, "attention: empty pool");
+  MI_CHECK(ceil_div(q_pos0 + T, block_size) <= MB, "block_table narrower than the context");
+  const uint16_t* kp = reinterpret_cast<const uint16_t*>(pool);
+  const uint16_t* vp = kp + (size_t)num_blocks * nkv * block_size * hd;
+  return launch_attn_prefill(reinterpret_cast<const uint16_t*>(q), T, q_pos0, kp, vp, block_size, block_table, nh, nkv,
+                             hd, reinterpret_cast<uint16_t*>(out), (hipStream_t)stream, window);
 }
 int mi_op_kv_write_f8(const void* k, const void* v, const int64_t* slots, int32_t T, int32_t nkv, int32_t hd, void* pool_u8,
                       int32_t num_blocks, int32_t block_size, float k_scale, float v_scale, void* stream) {

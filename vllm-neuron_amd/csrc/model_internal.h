@@ -58,6 +58,7 @@ struct mi_ctx {
   // KV pool: [L][2][NB][nkv_l][bs][hd] bf16, or e4m3 bytes (cfg.kv_cache_dtype = MI_KV_F8E4M3)
   uint16_t* kv_pool = nullptr;
   size_t kv_half = 0;  // elements of one K (or V) pool of one layer
+  int window = 0;      // sliding window every attention launch of this context takes: cfg.sliding_window, 0 where it is >= max_model_len
   bool kv_f8() const { return cfg.kv_cache_dtype == MI_KV_F8E4M3; }
   size_t kv_esz() const { return kv_f8() ? 1 : 2; }
   std::vector<float> k_scale, v_scale;   // FP8 KV: per-layer static scales (default 1.0)

@@ -464,6 +464,7 @@ class MI355XCausalLM(MI355XModelBase):
             return None
         files = sorted(glob.glob(os.path.join(model_name_or_path, "*.safetensors")))
         ident = [(os.path.basename(f), os.path.getsize(f), int(os.path.getmtime(f))) for f in files]
+        geo = {k: v for k, v in geo.items() if k != "sliding_window"}   # the images do not depend on the window
         key = json.dumps({"geo": geo, "quantized": quantized, "dtype": qdtype if quantized else "bf16",
                           "type": qtype if quantized else None, "tp": tp_degree,
                           "lm_head": not any("lm_head" in m for m in (cfg.get("modules_to_not_convert") or [])),
@@ -507,7 +508,14 @@ def _decoder_geometry(hf) -> dict:
         qkv_bias=int(getattr(hf, "model_type", "") == "qwen2" or bool(getattr(hf, "attention_bias", False))),
         tie_word_embeddings=int(bool(getattr(hf, "tie_word_embeddings", False))),
         # Qwen3: RMSNorm over head_dim on every q and k head (self_attn.q_norm / k_norm) before RoPE
-        qk_norm=int(getattr(hf, "model_type", "") == "qwen3"))
+        qk_norm=int(getattr(hf, "model_type", "") == "qwen3"),
+        # Mistral: one window for every layer.  (Qwen2's use_sliding_window / max_window_layers is per layer: ignored.)
+        sliding_window=_mistral_window(hf))
+
+
+def _mistral_window(hf) -> int:
+    w = getattr(hf, "sliding_window", None)
+    return int(w) if getattr(hf, "model_type", "") == "mistral" and isinstance(w, int) and w > 0 else 0
 
 
 def _get_model_configs(config) -> tuple[str, int, int]:
