@@ -104,13 +104,19 @@ typedef struct mi_model_config {
    * Token generation walks only the K/V tiles the window touches, context encoding takes the windowed launch geometry
    * once a sequence's keys outgrow W.  Blocks outside the window stay the caller's to keep or free. */
   int32_t sliding_window;
+  /* Context-encoding GEMMs (rows > 16) on INT8 weights take per-token dynamically quantized INT8 activations
+   * (s = amax / 127, an all-zero token s = 1; code = (int8) rint(clamp(x / s, -127, 127))) and run on the integer matrix
+   * core (v_mfma_i32_16x16x64_i8, exact int32 sum) on the weight image as stored.  The sibling of prefill_fp8_activations
+   * for quantization_dtype "int8"; projections it cannot serve (bf16 lm_head, K % 128 != 0, K > 131072, FP8 or bf16
+   * weights) and token generation keep the weight-only kernels.  0 = everything as before (the default). */
+  int32_t prefill_int8_activations;
 } mi_model_config;
 enum { MI_KV_BF16 = 0, MI_KV_F8E4M3 = 1 };
 #define MI_TP_ALL_RANKS (-1)
 enum { MI_TP_TRANSPORT_P2P = 0, MI_TP_TRANSPORT_RCCL = 1 };
 
 const char* mi_last_error(void);
-int mi_version(void);   /* 8 = this header (+ sliding_window, mi_op_paged_attn_decode_sw, mi_op_paged_attn_prefill_sw: Mistral); 7 lacked them (+ qk_norm, mi_op_qk_norm_rope_kv: Qwen3); 6 lacked them (+ mi_op_paged_attn_prefill_f8: context encoding reads the FP8 pool natively); 5 lacked it (+ kv_cache_dtype and the FP8-KV entry points mi_op_kv_write_f8, mi_op_paged_attn_decode_f8, mi_op_kv_dequant_gather); 4 lacked them (+ mi_tp_plan, mi_tp_info); 3 lacked those; 2 lacked tp_device_ids / tp_transport / MI_TP_ALL_RANKS; 1 lacked mi_forward_tokens, mi_op_sample, mi_tp_init_transport */
+int mi_version(void);   /* 9 = this header (+ prefill_int8_activations, mi_op_qlinear_a8_i8: INT8 x INT8 context-encoding GEMM); 8 lacked them (+ sliding_window, mi_op_paged_attn_decode_sw, mi_op_paged_attn_prefill_sw: Mistral); 7 lacked them (+ qk_norm, mi_op_qk_norm_rope_kv: Qwen3); 6 lacked them (+ mi_op_paged_attn_prefill_f8: context encoding reads the FP8 pool natively); 5 lacked it (+ kv_cache_dtype and the FP8-KV entry points mi_op_kv_write_f8, mi_op_paged_attn_decode_f8, mi_op_kv_dequant_gather); 4 lacked them (+ mi_tp_plan, mi_tp_info); 3 lacked those; 2 lacked tp_device_ids / tp_transport / MI_TP_ALL_RANKS; 1 lacked mi_forward_tokens, mi_op_sample, mi_tp_init_transport */
 
 int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out);
 int mi_ctx_destroy(mi_ctx* ctx);
@@ -332,6 +338,13 @@ int mi_op_qlinear(const void* x_bf16, int32_t M, const void* w_tiled, const floa
  * (scale amax/448) and multiplied on v_mfma_scale_f32_16x16x128_f8f6f4. */
 int mi_op_qlinear_a8(const void* x_bf16, int32_t M, const void* w_tiled, const float* scale,
                      const float* bias, int32_t N, int32_t K, float* y, void* stream);
+/* INT8-activation form (ABI 9; int8 weights, K % 128 == 0, K <= 131072, N % 16 == 0, else MI_EINVAL): x is quantized
+ * per token to int8 (s = amax / 127, all-zero row s = 1, code = rint(clamp(x / s, -127, 127))) and multiplied on
+ * v_mfma_i32_16x16x64_i8 with an exact int32 sum.  k_slices 0 or 1: no K-split; >= 2: the K-split kernel over that many
+ * slices of K / 128 steps (<= K / 128, else MI_EINVAL) into an fp32 slab the call allocates and frees, summed in slice
+ * order. */
+int mi_op_qlinear_a8_i8(const void* x_bf16, int32_t M, const void* w_tiled, const float* scale,
+                        const float* bias, int32_t N, int32_t K, int32_t k_slices, float* y, void* stream);
 /* y[T, H] bf16 = rmsnorm(x[T, H] fp32) * g */
 int mi_op_rmsnorm(const float* x, const float* g, int32_t T, int32_t H, float eps, void* y_bf16,
                   void* stream);

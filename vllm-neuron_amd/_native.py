@@ -43,6 +43,7 @@ class MiModelConfig(C.Structure):
         ("use_graphs", C.c_int32), ("prefill_fp8_activations", C.c_int32),
         ("tp_device_ids", C.c_int32 * 16), ("tp_transport", C.c_int32),
         ("kv_cache_dtype", C.c_int32), ("qk_norm", C.c_int32), ("sliding_window", C.c_int32),
+        ("prefill_int8_activations", C.c_int32),
     ]
 
 
@@ -121,6 +122,8 @@ _SIGS = {
                                 C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "mi_op_qlinear_a8": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                    C.c_int32, C.c_void_p, C.c_void_p]),
+    "mi_op_qlinear_a8_i8": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mi_op_rmsnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
                                 C.c_void_p]),
     "mi_op_kv_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

@@ -77,6 +77,15 @@ int launch_gemm_a8(const LinearW& w, int T, const uint8_t* x8, int ldx, int epi,
 bool gemm_a8_supported(const LinearW& w);
 // bf16 rows -> K-step-major e4m3 image [K / 128][T][128 B] + per-row scale (amax / 448; all-zero row -> 1)
 int launch_rowquant_fp8(const uint16_t* x, int T, int K, int ldx, uint8_t* x8, float* row_scale, hipStream_t s);
+// M > 16 with INT8 activations on INT8 weights: x8 = the same K-step-major image holding int8 codes as
+// launch_rowquant_i8 writes it (rule: rowquant_i8_code, mi_common.h), v_mfma_i32_16x16x64_i8 on the weight image as
+// stored, exact int32 sum.  supported: int8 weights, K % 128 == 0, N % 16 == 0, K <= 131072 (no int32 overflow).
+// force_ks (tests / mi_op_qlinear_a8_i8): that many K-slices instead of gemm_pick_splitk's choice; <= K / 128.
+int launch_gemm_a8i(const LinearW& w, int T, const uint8_t* x8, int ldx, int epi, const EpiArgs& e, hipStream_t s,
+                    float* splitk_ws = nullptr, size_t splitk_ws_bytes = 0, SlabSum* defer = nullptr, int force_ks = 0);
+bool gemm_a8i_supported(const LinearW& w);
+// bf16 rows -> K-step-major int8 image [K / 128][T][128 B] + per-row scale (amax / 127; all-zero row -> 1); K % 128 == 0
+int launch_rowquant_i8(const uint16_t* x, int T, int K, int ldx, uint8_t* x8, float* row_scale, hipStream_t s);
 size_t gemv_lds_bytes(int M, int K);
 bool gemv_fits(int M, int K);
 

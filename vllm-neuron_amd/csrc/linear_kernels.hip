@@ -2380,6 +2380,179 @@ int launch_gemm_a8(const LinearW& w, int T, const uint8_t* x8, int ldx, int epi,
 }
 
 // =====================================================================================
+// GEMM with INT8 activations (context encoding on INT8 weights, integer matrix core)
+// =====================================================================================
+// y[m, n] = (sum_k q_x[m, k] * q_w[n, k]) * s_w[n] * s_x[m]   both operands int8, the sum in int32 (exact).
+// v_mfma_i32_16x16x64_i8 takes 16 bytes of one row per lane from each operand: lane (g = lane >> 4, r = lane & 15) of a
+// stored weight tile holds row r, 16-byte chunk g of the tile's 64 columns, which IS the A operand -- the weight image goes
+// from global memory into the matrix core as stored, one 16-byte load per (n-tile, k-tile) per lane, no decode8 and no
+// repacking.  The B operand is the same 16 bytes of a token row: chunk g of k-tile 2ks at g * 16 of the 128-byte K-step
+// row, chunk g of k-tile 2ks + 1 at g * 16 + 64.
+//
+// Work split: work-group = 4 waves, tile 128 (n) x 128 (m) x 128 K bytes.  Wave w owns n-tiles 2w, 2w + 1 against all
+// 8 m-tiles: 2 x 8 x 2 = 32 MFMAs a K-step on 4 weight fragments (64 B a lane) and 16 B-fragment reads from LDS, each
+// B fragment feeding both n-tiles.  XCD-aware tile order as in gemm_a8_kernel.
+// LDS image: two stages of 128 token rows x 128 B at a 160-byte pitch (kA8Pitch: the fragment reads are conflict-free),
+// 40 KiB.  K-step ks + 1 is fetched into registers before the MFMAs of K-step ks and stored to the OTHER stage after
+// them, so a K-step costs one barrier, not two: the stage being overwritten was last read one K-step ago, and every wave
+// has passed the barrier since.  (The integer MFMA has half the K depth of the scaled one, so there are twice as many
+// matrix instructions per barrier-to-barrier span to keep fed; the single-stage form of gemm_a8_kernel leaves the matrix
+// core idle over both of its barriers.)
+// Registers per lane: 64 i32 accumulators, 16 + 16 weight fragment (current / next), 16 staged activations, 8 B operand:
+// about 130, which with 40 KiB of LDS leaves room for three resident work-groups per CU (3 waves per SIMD, 120 KiB) to
+// hide each other's load latency -- why this tile and not 256 x 128, see launch_gemm_a8.
+// The accumulators are converted to fp32 once, after the K loop (|sum| <= 127 * 127 * K < 2^31 for K <= 131072: the
+// integer sum cannot overflow; the i32 16x16 result has the lane layout of the f32 one), and go through epilogue<EPI>.
+// SPLIT: as gemm_a8_kernel -- each K-slice's integer partial, converted once, to slab[z][m][n]; the sum of the slabs is
+// exact in fp32 while it stays below 2^24 and correctly rounded per addition beyond.
+typedef __attribute__((ext_vector_type(4))) int i32x4_t;
+constexpr int kA8iMaxK = 131072;
+constexpr int kA8iStage = kA8BM * kA8Pitch;   // 20 KiB
+
+template <int EPI, bool SPLIT>
+__global__ __launch_bounds__(256) void gemm_a8i_kernel(const uint4* __restrict__ W, int NT, int KT, int T, int K,
+                                                       const uint8_t* __restrict__ x8, int ldx, EpiArgs e,
+                                                       float* __restrict__ slab) {
+  __shared__ __attribute__((aligned(16))) unsigned char xs[2 * kA8iStage];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int g = lane >> 4, c = lane & 15;
+  constexpr int NTW = 2, BNT = 4 * NTW;   // n-tiles per wave / per work-group
+  const int mtiles = ceil_div(T, kA8BM), ntiles = ceil_div(NT, BNT);
+  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
+  const int mblk = seq % mtiles, nblk = (seq / mtiles) * 8 + xcd;
+  if (nblk >= ntiles) return;
+  const int m0 = mblk * kA8BM, nt0 = nblk * BNT + wave * NTW;
+  const int nks_all = K / kA8BK;
+  const int ks_per = SPLIT ? ceil_div(nks_all, (int)gridDim.z) : nks_all;
+  const int ks_beg = SPLIT ? (int)blockIdx.z * ks_per : 0;
+  const int nks = min(ks_beg + ks_per, nks_all);   // exclusive end of this slice (an empty slice writes zeros)
+
+  i32x4_t acc[NTW][8];
+#pragma unroll
+  for (int i = 0; i < NTW; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[i][j] = i32x4_t{0, 0, 0, 0};
+
+  // x staging: 128 rows x 128 B per K-step = 1024 chunks of 16 B, 4 per thread, 16 KiB contiguous in the K-step-major image
+  // (rows past T are computed on a copy of the last row, never stored; n-tiles past NT likewise on the last tile)
+  const uint8_t* xsrc[4];
+  int xdst[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int idx = tid + i * 256, row = idx >> 3, ch = idx & 7;
+    xsrc[i] = x8 + (size_t)min(m0 + row, T - 1) * kA8BK + ch * 16;
+    xdst[i] = row * kA8Pitch + ch * 16;
+  }
+  const uint4* wsrc[NTW];
+#pragma unroll
+  for (int i = 0; i < NTW; ++i) wsrc[i] = W + (size_t)min(nt0 + i, NT - 1) * KT * 64 + lane;
+  u32x4_t xr[4], wr[NTW][2], wn[NTW][2];
+  auto load_x = [&](int ks) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xr[i] = *reinterpret_cast<const u32x4_t*>(xsrc[i] + (size_t)ks * ldx * kA8BK);
+  };
+  auto store_x = [&](int stage) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4_t*>(&xs[stage * kA8iStage + xdst[i]]) = xr[i];
+  };
+  auto load_w = [&](u32x4_t (&dst)[NTW][2], int ks) {
+#pragma unroll
+    for (int i = 0; i < NTW; ++i)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) dst[i][t] = *reinterpret_cast<const u32x4_t*>(wsrc[i] + (size_t)(ks * 2 + t) * 64);
+  };
+  if (ks_beg < nks) {
+    load_x(ks_beg);
+    load_w(wr, ks_beg);
+    store_x(ks_beg & 1);
+  }
+  __syncthreads();
+  for (int ks = ks_beg; ks < nks; ++ks) {
+    const bool more = ks + 1 < nks;
+    if (more) {
+      load_x(ks + 1);
+      load_w(wn, ks + 1);
+    }
+    const unsigned char* xrow = &xs[(ks & 1) * kA8iStage + c * kA8Pitch + g * 16];
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) {
+      const i32x4_t b0 = *reinterpret_cast<const i32x4_t*>(xrow + mt * 16 * kA8Pitch);        // k-tile 2ks,     chunk g
+      const i32x4_t b1 = *reinterpret_cast<const i32x4_t*>(xrow + mt * 16 * kA8Pitch + 64);   // k-tile 2ks + 1, chunk g
+#pragma unroll
+      for (int i = 0; i < NTW; ++i) {
+        acc[i][mt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4_t, wr[i][0]), b0, acc[i][mt], 0, 0, 0);
+        acc[i][mt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4_t, wr[i][1]), b1, acc[i][mt], 0, 0, 0);
+      }
+    }
+    if (more) {
+      store_x((ks + 1) & 1);   // the other stage: read last in K-step ks - 1, before the barrier every wave has passed
+#pragma unroll
+      for (int i = 0; i < NTW; ++i) {
+        wr[i][0] = wn[i][0];
+        wr[i][1] = wn[i][1];
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < NTW; ++i) {
+    if (nt0 + i >= NT) continue;
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) {
+      const int m = m0 + mt * 16 + c;
+      if (m >= T) continue;
+      const int n0 = (nt0 + i) * 16 + g * 4;
+      const f32x4_t v = {(float)acc[i][mt][0], (float)acc[i][mt][1], (float)acc[i][mt][2], (float)acc[i][mt][3]};
+      if constexpr (SPLIT) {
+        *reinterpret_cast<float4*>(slab + ((size_t)blockIdx.z * T + m) * (NT * 16) + n0) = make_float4(v[0], v[1], v[2], v[3]);
+      } else {
+        epilogue<EPI>(e, m, n0, v);
+      }
+    }
+  }
+}
+
+bool gemm_a8i_supported(const LinearW& w) {
+  return w.wd == MI_W_INT8 && w.K % kA8BK == 0 && w.N % 16 == 0 && w.K <= kA8iMaxK;
+}
+
+int launch_gemm_a8i(const LinearW& w, int T, const uint8_t* x8, int ldx, int epi, const EpiArgs& e, hipStream_t s,
+                    float* splitk_ws, size_t splitk_ws_bytes, SlabSum* defer, int force_ks) {
+  if (defer) *defer = SlabSum();
+  MI_CHECK(T >= 1, "gemm_a8i: T must be >= 1");
+  MI_CHECK(gemm_a8i_supported(w), "gemm_a8i: needs int8 weights, K % 128 == 0, K <= 131072, N % 16 == 0");
+  MI_CHECK(ldx >= T && e.row_scale != nullptr, "gemm_a8i: x8 is the K-step-major image of >= T rows, with its row scales");
+  const int NT = w.N / 16, KT = w.K / 64, nks = w.K / kA8BK;
+  const int mtiles = ceil_div(T, kA8BM), ntiles = ceil_div(w.N, 128);
+  int KS = gemm_pick_splitk(mtiles * ntiles, nks, T, w.N, splitk_ws ? splitk_ws_bytes : 0);
+  if (force_ks) {
+    MI_CHECK(force_ks >= 1 && force_ks <= nks && (force_ks == 1 || (splitk_ws && (size_t)force_ks * T * w.N * 4 <= splitk_ws_bytes)),
+             "gemm_a8i: forced K-split must not exceed K / 128 and must fit the workspace");
+    KS = force_ks;
+  }
+  const uint4* W = reinterpret_cast<const uint4*>(w.w);
+  dim3 grid(8 * mtiles * ceil_div(ntiles, 8), 1, KS);   // see gemm_a8_kernel: XCD-aware tile order
+#define MI_A8I(EPI_) \
+  do { \
+    if (KS == 1) { \
+      hipLaunchKernelGGL((gemm_a8i_kernel<EPI_, false>), grid, dim3(256), 0, s, W, NT, KT, T, w.K, x8, ldx, e, nullptr); \
+    } else { \
+      hipLaunchKernelGGL((gemm_a8i_kernel<EPI_, true>), grid, dim3(256), 0, s, W, NT, KT, T, w.K, x8, ldx, e, splitk_ws); \
+      if (defer && EPI_ == EPI_RESID) { *defer = SlabSum{splitk_ws, KS, T, w.N, e.scale, e.bias, e.row_scale}; } \
+      else hipLaunchKernelGGL((splitk_reduce_kernel<EPI_>), dim3(ceil_div(T * (w.N / 4), 256)), dim3(256), 0, s, splitk_ws, KS, T, w.N, e); \
+    } \
+  } while (0)
+  if (epi == EPI_QKV) MI_A8I(EPI_QKV);
+  else if (epi == EPI_QKV_F8) MI_A8I(EPI_QKV_F8);
+  else if (epi == EPI_SWIGLU) MI_A8I(EPI_SWIGLU);
+  else if (epi == EPI_RESID) MI_A8I(EPI_RESID);
+  else MI_A8I(EPI_F32);
+#undef MI_A8I
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+// =====================================================================================
 // Load-time quantize + tile
 // =====================================================================================
 __global__ void rowmax_kernel(const float* __restrict__ w, int ld, float* __restrict__ rowmax) {
@@ -2476,6 +2649,60 @@ __global__ __launch_bounds__(256) void rowquant_fp8_kernel(const uint16_t* __res
 int launch_rowquant_fp8(const uint16_t* x, int T, int K, int ldx, uint8_t* x8, float* row_scale, hipStream_t s) {
   MI_CHECK(K % 8 == 0 && ldx % 8 == 0, "rowquant: K and the row stride must be multiples of 8");
   hipLaunchKernelGGL(rowquant_fp8_kernel, dim3(T), dim3(256), 0, s, x, K, ldx, x8, row_scale);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+// bf16 activations -> int8 + per-token scale, the rule of mi_common.h (rowquant_i8_code).  One work-group per row;
+// the row stays in registers between the amax pass and the quantize pass as in rowquant_fp8_kernel (K <= 16384), longer
+// rows are re-read.  Same K-step-major image.
+__device__ __forceinline__ float bf16x8_amax(const u32x4_t r, float amax) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) amax = fmaxf(amax, fmaxf(fabsf(bf16lo_to_f32(r[k])), fabsf(bf16hi_to_f32(r[k]))));
+  return amax;
+}
+__global__ __launch_bounds__(256) void rowquant_i8_kernel(const uint16_t* __restrict__ x, int K, int ldx,
+                                                          uint8_t* __restrict__ x8, float* __restrict__ row_scale) {
+  __shared__ float red[4];
+  const int t = blockIdx.x, tid = threadIdx.x;
+  const uint16_t* row = x + (size_t)t * ldx;
+  const int nchunk = K / 8;
+  u32x4_t v[kRqMax];
+  float amax = 0.f;
+#pragma unroll
+  for (int q = 0; q < kRqMax; ++q) {
+    const int c8 = tid + q * 256;
+    v[q] = c8 < nchunk ? *reinterpret_cast<const u32x4_t*>(row + c8 * 8) : u32x4_t{0, 0, 0, 0};
+  }
+#pragma unroll
+  for (int q = 0; q < kRqMax; ++q) amax = bf16x8_amax(v[q], amax);
+  for (int c8 = tid + kRqMax * 256; c8 < nchunk; c8 += 256) amax = bf16x8_amax(*reinterpret_cast<const u32x4_t*>(row + c8 * 8), amax);
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
+  if ((tid & 63) == 0) red[tid >> 6] = amax;
+  __syncthreads();
+  amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  const float scale = amax > 0.f ? amax / 127.f : 1.f;
+  if (tid == 0) row_scale[t] = scale;
+  auto emit = [&](const u32x4_t r, int c8) {
+    uint32_t o[2] = {0, 0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      o[k >> 1] |= (rowquant_i8_code(bf16lo_to_f32(r[k]), scale) | (rowquant_i8_code(bf16hi_to_f32(r[k]), scale) << 8)) << (16 * (k & 1));
+    const int k0 = c8 * 8;
+    *reinterpret_cast<uint2*>(x8 + ((size_t)(k0 >> 7) * gridDim.x + t) * 128 + (k0 & 127)) = make_uint2(o[0], o[1]);
+  };
+#pragma unroll
+  for (int q = 0; q < kRqMax; ++q) {
+    const int c8 = tid + q * 256;
+    if (c8 < nchunk) emit(v[q], c8);
+  }
+  for (int c8 = tid + kRqMax * 256; c8 < nchunk; c8 += 256) emit(*reinterpret_cast<const u32x4_t*>(row + c8 * 8), c8);
+}
+
+int launch_rowquant_i8(const uint16_t* x, int T, int K, int ldx, uint8_t* x8, float* row_scale, hipStream_t s) {
+  MI_CHECK(K % 128 == 0 && ldx % 8 == 0, "rowquant_i8: K % 128 == 0 and a row stride that is a multiple of 8 required");
+  hipLaunchKernelGGL(rowquant_i8_kernel, dim3(T), dim3(256), 0, s, x, K, ldx, x8, row_scale);
   MI_HIP(hipGetLastError());
   return MI_OK;
 }

@@ -125,6 +125,14 @@ __device__ __forceinline__ uint32_t f32_to_e4m3fn(float f) {
   return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(c, 0.f, 0, false) & 0xffu;
 }
 
+// INT8 activations, the one statement of the rule: per token s = amax / 127.f (an all-zero row: s = 1), and
+// code = (int8) rintf(clamp(x / s, -127, 127)) -- true division and round-half-even, so that a restatement in fp32 on the
+// CPU (torch.round(x / s).clamp(-127, 127)) gives the same codes.  rowquant_i8_kernel and the INT8 form of the row norm
+// both go through this function.  Returns the code's byte.
+__device__ __forceinline__ uint32_t rowquant_i8_code(float x, float s) {
+  return (uint32_t)(int)rintf(__builtin_fminf(__builtin_fmaxf(x / s, -127.f), 127.f)) & 0xffu;
+}
+
 // FP8 KV cache, write rule: four bf16-rounded K (or V) values of one row -> four e4m3 codes (one 4-byte store).
 // code = rne_e4m3(clamp(float(x_bf16) * inv, -448, 448)), inv = 1.0f / scale computed once on the host.  Every writer
 // of the byte pool goes through this function, so the stand-alone write and a GEMM epilogue give the same bytes.

@@ -12,6 +12,9 @@ int launch_norm_rows(const float* resid_in, const float* partial, float* resid_o
 // K-step-major image [H / 128][T][128 B] + row_scale[T]
 int launch_norm_rows_fp8(const float* resid_in, const float* partial, float* resid_out, const float* gain, int T,
                          int H, float eps, uint8_t* x8, float* row_scale, hipStream_t s, const SlabSum* slabs = nullptr);
+// ... and as the INT8 GEMM's input: bf16-rounded, then int8 by rowquant_i8_code (mi_common.h), same image
+int launch_norm_rows_i8(const float* resid_in, const float* partial, float* resid_out, const float* gain, int T,
+                        int H, float eps, uint8_t* x8, float* row_scale, hipStream_t s, const SlabSum* slabs = nullptr);
 // dst[i, :] = src[rows[i], :]   (fp32 rows of H elements, H % 4 == 0)
 // ---- fused speculation (model.hip, mi_forward_spec) ----
 // After draft step `step` (0-based): the draft's sampled tokens become (a) candidate step + 1 of every

@@ -132,6 +132,7 @@ int run_linear(mi_ctx* c, const Linear& L, int rows, int pro, ProArgs p, int epi
   const uint16_t* x = p.x;
   int ldx = p.ldx;
   const bool a8 = c->cfg.prefill_fp8_activations && gemm_a8_supported(L.view());
+  const bool a8i = c->cfg.prefill_int8_activations && gemm_a8i_supported(L.view());   // INT8 weights: never both
   if (pro == PRO_NORM) {
     Scope sc(c, MI_K_OTHER);
     // A K-split residual projection in front of this norm left its slabs unsummed: the norm sums them on the way
@@ -150,6 +151,8 @@ int run_linear(mi_ctx* c, const Linear& L, int rows, int pro, ProArgs p, int epi
     }
     if (a8) {   // norm and per-token quantization in one pass over the row
       MI_TRY(launch_norm_rows_fp8(rin, p.partial, rout, p.gain, rows, L.K, p.eps, c->x8, c->x8_scale, c->stream, slabs));
+    } else if (a8i) {
+      MI_TRY(launch_norm_rows_i8(rin, p.partial, rout, p.gain, rows, L.K, p.eps, c->x8, c->x8_scale, c->stream, slabs));
     } else {
       MI_TRY(launch_norm_rows(rin, p.partial, rout, p.gain, rows, L.K, p.eps, c->xn, c->stream, slabs));
       x = c->xn;
@@ -174,6 +177,17 @@ int run_linear(mi_ctx* c, const Linear& L, int rows, int pro, ProArgs p, int epi
     e.row_scale = c->x8_scale;
     Scope sc(c, MI_K_GEMM);
     MI_TRY(launch_gemm_a8(L.view(), rows, c->x8, rows, epi, e, c->stream, c->splitk_ws, c->splitk_ws_bytes, defer));
+    note_deferred();
+    return MI_OK;
+  }
+  if (a8i) {   // INT8 weights: per-token int8 activations on the integer matrix core
+    if (pro != PRO_NORM) {
+      Scope sc(c, MI_K_OTHER);
+      MI_TRY(launch_rowquant_i8(x, rows, L.K, ldx, c->x8, c->x8_scale, c->stream));
+    }
+    e.row_scale = c->x8_scale;
+    Scope sc(c, MI_K_GEMM);
+    MI_TRY(launch_gemm_a8i(L.view(), rows, c->x8, rows, epi, e, c->stream, c->splitk_ws, c->splitk_ws_bytes, defer));
     note_deferred();
     return MI_OK;
   }
@@ -640,7 +654,7 @@ int capture_or_launch_decode(mi_ctx* c, int B, int MB) {
 extern "C" {
 
 const char* mi_last_error(void) { return mi::g_err.c_str(); }
-int mi_version(void) { return 8; }   // 8: + sliding_window, mi_op_paged_attn_decode_sw / mi_op_paged_attn_prefill_sw (Mistral); 7: + qk_norm, mi_op_qk_norm_rope_kv (Qwen3); 6: + mi_op_paged_attn_prefill_f8; 5: + kv_cache_dtype, mi_op_kv_write_f8 / mi_op_paged_attn_decode_f8 / mi_op_kv_dequant_gather; 4: + mi_tp_plan, mi_tp_info; 3: + in-process tensor parallelism (tp_rank = MI_TP_ALL_RANKS, tp_device_ids, tp_transport)
+int mi_version(void) { return 9; }   // 9: + prefill_int8_activations, mi_op_qlinear_a8_i8 (INT8 x INT8 context-encoding GEMM); 8: + sliding_window, mi_op_paged_attn_decode_sw / mi_op_paged_attn_prefill_sw (Mistral); 7: + qk_norm, mi_op_qk_norm_rope_kv (Qwen3); 6: + mi_op_paged_attn_prefill_f8; 5: + kv_cache_dtype, mi_op_kv_write_f8 / mi_op_paged_attn_decode_f8 / mi_op_kv_dequant_gather; 4: + mi_tp_plan, mi_tp_info; 3: + in-process tensor parallelism (tp_rank = MI_TP_ALL_RANKS, tp_device_ids, tp_transport)
 
 int mi_tp_plan(const mi_model_config* cfg, int32_t rank, mi_tp_plan_t* out) {
   MI_CHECK(cfg && out, "null argument");
@@ -1042,7 +1056,7 @@ static size_t workspace_estimate(const mi_ctx* c) {
   const mi_model_config& k = c->cfg;
   const size_t R = (size_t)c->max_rows, H = (size_t)c->H;
   size_t b = 3 * R * H * 4 + R * std::max<size_t>(H, c->I_l) * 2 + 2 * R * c->q_dim * 2 + R * c->I_l * 2;
-  if (k.prefill_fp8_activations) b += R * std::max<size_t>(std::max<size_t>(H, c->I_l), c->q_dim) + R * 4;
+  if (k.prefill_fp8_activations || k.prefill_int8_activations) b += R * std::max<size_t>(std::max<size_t>(H, c->I_l), c->q_dim) + R * 4;
   if (k.qk_norm) b += R * (c->q_dim + 2 * (size_t)c->kv_dim) * 4;            // fp32 QKV in front of the per-head norm
   b += (size_t)64 << 20;                                                   // split-K workspace
   b += (size_t)k.max_num_seqs * c->V_l * 4 * (1 + (k.tp_degree > 1 ? k.tp_degree : 0));
@@ -1143,7 +1157,7 @@ int mi_finalize(mi_ctx* c) {
   MI_TRY(dmalloc(&c->attn_out, R * c->q_dim, ws));
   MI_TRY(dmalloc(&c->act, R * c->I_l, ws));
   if (k.qk_norm) MI_TRY(dmalloc(&c->qkv_f32, R * (c->q_dim + 2 * c->kv_dim), ws));
-  if (k.prefill_fp8_activations) {
+  if (k.prefill_fp8_activations || k.prefill_int8_activations) {
     MI_TRY(dmalloc(&c->x8, R * std::max(std::max(c->H, c->I_l), c->q_dim), ws));
     MI_TRY(dmalloc(&c->x8_scale, R, ws));
   }
@@ -1907,6 +1921,36 @@ int mi_op_qlinear_a8(const void* x, int32_t M, const void* w_tiled, const float*
   hipStreamSynchronize(s);
   hipFree(x8);
   hipFree(xs);
+  return rc;
+}
+int mi_op_qlinear_a8_i8(const void* x, int32_t M, const void* w_tiled, const float* scale, const float* bias, int32_t N,
+                        int32_t K, int32_t k_slices, float* y, void* stream) {
+  MI_CHECK(x && w_tiled && scale && y && M >= 1, "null argument");
+  LinearW W{w_tiled, N, K, MI_W_INT8};
+  MI_CHECK(gemm_a8i_supported(W), "qlinear_a8_i8: needs K % 128 == 0, K <= 131072 and N % 16 == 0");
+  MI_CHECK(k_slices >= 0 && k_slices <= K / 128, "qlinear_a8_i8: k_slices must not exceed K / 128");
+  const int ks = k_slices >= 2 ? k_slices : 1;
+  const size_t slab_bytes = ks > 1 ? (size_t)ks * M * N * 4 : 0;
+  uint8_t* x8 = nullptr;
+  float *xs = nullptr, *slab = nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  int rc = MI_OK;
+  if (hipMalloc(reinterpret_cast<void**>(&x8), (size_t)M * K) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&xs), (size_t)M * 4) != hipSuccess ||
+      (slab_bytes && hipMalloc(reinterpret_cast<void**>(&slab), slab_bytes) != hipSuccess)) {
+    set_error("qlinear_a8_i8: out of device memory");
+    rc = MI_EHIP;
+  }
+  if (rc == MI_OK) rc = launch_rowquant_i8(reinterpret_cast<const uint16_t*>(x), M, K, K, x8, xs, s);
+  if (rc == MI_OK) {
+    EpiArgs e{};
+    e.scale = scale; e.bias = bias; e.out_f32 = y; e.ld_out = N; e.row_scale = xs;
+    rc = launch_gemm_a8i(W, M, x8, M, EPI_F32, e, s, slab, slab_bytes, nullptr, ks);
+  }
+  hipStreamSynchronize(s);
+  hipFree(x8);
+  hipFree(xs);
+  hipFree(slab);
   return rc;
 }
 int mi_op_rmsnorm(const float* x, const float* g, int32_t T, int32_t H, float eps, void* y, void* stream) {

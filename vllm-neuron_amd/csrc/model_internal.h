@@ -75,7 +75,7 @@ struct mi_ctx {
   float* partial = nullptr;
   uint16_t *xn = nullptr, *qbuf = nullptr, *attn_out = nullptr, *act = nullptr;
   float* qkv_f32 = nullptr;     // qk_norm: the QKV projection as fp32 [rows, q_dim + 2 kv_dim], input of the per-head norm
-  uint8_t* x8 = nullptr;        // FP8-activation GEMM input [rows, K]
+  uint8_t* x8 = nullptr;        // FP8- / INT8-activation GEMM input [rows, K]
   float* x8_scale = nullptr;    // its per-token scales [rows]
   float* splitk_ws = nullptr;   // fp32 K-split slabs of short-prompt GEMMs
   mi::SlabSum pend;               // a residual projection's K-split sum left for the next row norm (run_linear)

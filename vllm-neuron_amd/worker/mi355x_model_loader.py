@@ -18,6 +18,8 @@ working).  Extra keys understood here:
   tp_transport               "p2p" | "rccl" exchange between the rank shards of tensor_parallel_size > 1
   prefill_fp8_activations    bool           context-encoding GEMMs on FP8 weights quantize their bf16
                                             inputs per token to e4m3 and run on the MX-scaled MFMA
+  prefill_int8_activations   bool           the same for INT8 weights: per-token int8 inputs (scale amax / 127) on
+                                            the integer MFMA; off by default, no effect on FP8 / bf16 weights
 """
 
 from __future__ import annotations
@@ -315,6 +317,7 @@ class MI355XCausalLM(MI355XModelBase):
             device_id=int(kwargs.get("device_id", 0)),
             use_graphs=int(cfg.get("use_graphs", 1)),
             prefill_fp8_activations=int(bool(cfg.get("prefill_fp8_activations", False))),
+            prefill_int8_activations=int(bool(cfg.get("prefill_int8_activations", False))),
             kv_cache_dtype=MI_KV[cfg.get("kv_cache_dtype", "auto")],
             **geo)
         if fused_spec:
@@ -430,6 +433,7 @@ class MI355XCausalLM(MI355XModelBase):
             tp_degree=1, tp_rank=0, device_id=int((kwargs.get("tp_device_ids") or [kwargs.get("device_id", 0)])[0]),
             use_graphs=int(cfg.get("use_graphs", 1)),
             prefill_fp8_activations=int(bool(cfg.get("prefill_fp8_activations", False))),
+            prefill_int8_activations=int(bool(cfg.get("prefill_int8_activations", False))),
             kv_cache_dtype=self.model.cfg.kv_cache_dtype, **geo)   # the draft's pool takes the target's dtype
         synthetic, state_dict = cfg.get("draft_synthetic_weights"), cfg.get("draft_state_dict")
         if synthetic is not None:
