@@ -44,7 +44,16 @@ extern "C" {
 /* element types for host/device tensors crossing the ABI */
 enum { MI_F32 = 0, MI_BF16 = 1, MI_F8E4M3 = 2, MI_I8 = 3, MI_I64 = 4, MI_I32 = 5 };
 /* weight storage dtypes ("quantization_dtype", loader.py:895-896) */
-enum { MI_W_BF16 = 0, MI_W_F8E4M3 = 1, MI_W_INT8 = 2 };
+enum { MI_W_BF16 = 0, MI_W_F8E4M3 = 1, MI_W_INT8 = 2, MI_W_MXFP4 = 3 };
+/* MI_W_MXFP4 (ABI 10): OCP microscaling FP4, weight-only.  Blocks are 32 consecutive K elements of one output row; K % 128 == 0
+ * and N % 16 == 0 are required (else MI_EINVAL).  Per block: amax = max |w|; amax == 0: E = 0 and all codes 0; otherwise
+ * E = clamp(floor(log2(amax)) - 2, -100, 100).  The scale byte is E + 127 (e8m0).  code = sign | e2m1_rne_sat(|w| * 2^-E) on the
+ * grid 0, 0.5, 1, 1.5, 2, 3, 4, 6: round to nearest, ties to the even code, magnitudes >= 6 saturate to 6, sign bit set for
+ * w < 0, a NaN becomes +6.  value = e2m1(code) * 2^E, which the clamp on E keeps a normal bf16: like FP8 and INT8 the format
+ * is decoded exactly and multiplied on the bf16 matrix core with fp32 accumulation.  quant_type is accepted and ignored; the
+ * per-row fp32 scale every epilogue multiplies by is 1.0f.  Image: N * K / 2 code bytes in 16-row x 128-k tiles, then the scale
+ * plane of N * ceil(K / 512) * 16 bytes (= N * K / 32 when K % 512 == 0), one allocation.  Tensor parallelism (tp_degree > 1)
+ * is refused for this dtype; prefill_fp8_activations / prefill_int8_activations are ignored (weight-only everywhere). */
 /* "quantization_type" (loader.py:892-894) */
 enum { MI_Q_PER_TENSOR_SYMMETRIC = 0, MI_Q_PER_CHANNEL_SYMMETRIC = 1 };
 enum { MI_ROPE_DEFAULT = 0, MI_ROPE_LLAMA3 = 1 };
@@ -116,7 +125,7 @@ enum { MI_KV_BF16 = 0, MI_KV_F8E4M3 = 1 };
 enum { MI_TP_TRANSPORT_P2P = 0, MI_TP_TRANSPORT_RCCL = 1 };
 
 const char* mi_last_error(void);
-int mi_version(void);   /* 9 = this header (+ prefill_int8_activations, mi_op_qlinear_a8_i8: INT8 x INT8 context-encoding GEMM); 8 lacked them (+ sliding_window, mi_op_paged_attn_decode_sw, mi_op_paged_attn_prefill_sw: Mistral); 7 lacked them (+ qk_norm, mi_op_qk_norm_rope_kv: Qwen3); 6 lacked them (+ mi_op_paged_attn_prefill_f8: context encoding reads the FP8 pool natively); 5 lacked it (+ kv_cache_dtype and the FP8-KV entry points mi_op_kv_write_f8, mi_op_paged_attn_decode_f8, mi_op_kv_dequant_gather); 4 lacked them (+ mi_tp_plan, mi_tp_info); 3 lacked those; 2 lacked tp_device_ids / tp_transport / MI_TP_ALL_RANKS; 1 lacked mi_forward_tokens, mi_op_sample, mi_tp_init_transport */
+int mi_version(void);   /* 10 = this header (+ MI_W_MXFP4: 4-bit block-scaled weights through weight_dtype, mi_op_quantize_weight, mi_op_untile_weight, mi_op_qlinear); 9 lacked it (+ prefill_int8_activations, mi_op_qlinear_a8_i8: INT8 x INT8 context-encoding GEMM); 8 lacked them (+ sliding_window, mi_op_paged_attn_decode_sw, mi_op_paged_attn_prefill_sw: Mistral); 7 lacked them (+ qk_norm, mi_op_qk_norm_rope_kv: Qwen3); 6 lacked them (+ mi_op_paged_attn_prefill_f8: context encoding reads the FP8 pool natively); 5 lacked it (+ kv_cache_dtype and the FP8-KV entry points mi_op_kv_write_f8, mi_op_paged_attn_decode_f8, mi_op_kv_dequant_gather); 4 lacked them (+ mi_tp_plan, mi_tp_info); 3 lacked those; 2 lacked tp_device_ids / tp_transport / MI_TP_ALL_RANKS; 1 lacked mi_forward_tokens, mi_op_sample, mi_tp_init_transport */
 
 int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out);
 int mi_ctx_destroy(mi_ctx* ctx);
@@ -322,15 +331,18 @@ int mi_op_sample_ws(const float* logits, int32_t B, int32_t V, const float* samp
 
 
 /* Quantize + re-tile a row-major fp32 [N, K] device matrix.  scale_out [N] fp32.
- * tiled_out: N*K bytes (fp8/int8) or 2*N*K (bf16), kernel-native 16-row tiles. */
+ * tiled_out: N*K bytes (fp8/int8) or 2*N*K (bf16), kernel-native 16-row tiles; MI_W_MXFP4: N*K/2 + N*ceil(K/512)*16 bytes
+ * (codes, then the scale plane), scale_out all 1.0f, quant_type ignored. */
 int mi_op_quantize_weight(const float* w, int32_t N, int32_t K, int32_t weight_dtype,
                           int32_t quant_type, void* tiled_out, float* scale_out, void* stream);
-/* Inverse of the tiling for inspection: q_out row-major [N, K] (1 or 2 bytes/elem). */
+/* Inverse of the tiling for inspection: q_out row-major [N, K] (1 or 2 bytes/elem).  MI_W_MXFP4: N*K/2 packed code bytes,
+ * row-major with even k in the low nibble, followed by N*K/32 scale bytes row-major [N, K/32]. */
 int mi_op_untile_weight(const void* tiled, int32_t N, int32_t K, int32_t weight_dtype,
                         void* q_out, void* stream);
 /* y[M, N] fp32 = (x[M, K] bf16 . Wq^T) * scale (+ bias).  M <= 16: weight-streaming GEMV;
  * else MFMA GEMM.  force_path: 0 auto, 1 GEMV, 2 GEMM (picked by size), 3 the wide-N LDS-DMA GEMM (1-byte weights),
- * 4 / 5 that GEMM with K split over 2 / 4 slices at 128-token blocks, 6 / 7 at 256-token blocks (K / 64 a multiple of the slices). */
+ * 4 / 5 that GEMM with K split over 2 / 4 slices at 128-token blocks, 6 / 7 at 256-token blocks (K / 64 a multiple of the slices).
+ * MI_W_MXFP4: gemv_w4_kernel (M <= 32) / gemm_w4_kernel; force_path 0, 1, 2 only (3 .. 7: MI_EINVAL). */
 int mi_op_qlinear(const void* x_bf16, int32_t M, const void* w_tiled, const float* scale,
                   const float* bias, int32_t N, int32_t K, int32_t weight_dtype, float* y,
                   int32_t force_path, void* stream);

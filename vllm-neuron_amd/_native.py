@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI355X_VLLM_LIB") or os.path.join(_HERE, "csrc", "libmi355x_vllm.so")
 
 MI_F32, MI_BF16 = 0, 1
-MI_W = {"bfloat16": 0, "bf16": 0, None: 0, "f8e4m3": 1, "fp8": 1, "int8": 2}
+MI_W = {"bfloat16": 0, "bf16": 0, None: 0, "f8e4m3": 1, "fp8": 1, "int8": 2, "mxfp4": 3}   # mxfp4: e2m1 codes + e8m0 scale per 32 K
 MI_Q = {"per_tensor_symmetric": 0, "per_channel_symmetric": 1}
 MI_KV = {"auto": 0, "bfloat16": 0, "fp8": 1, "fp8_e4m3": 1}    # vLLM cache_dtype -> mi_model_config.kv_cache_dtype
 KV_SCALE_SUFFIXES = ("self_attn.k_scale", "self_attn.v_scale")   # scalar fp32 per layer (vLLM checkpoint names)

@@ -103,6 +103,7 @@ struct QuantJob {
   int dst_row0;        // first destination row (ROWMAP_EVERY_OTHER: row of element 0)
   int wd, quant_type;
   void* dst;           // tiled destination matrix [dstN, K]
+  int dst_rows;        // dstN (MI_W_MXFP4: the scale plane lies behind the dstN * K / 2 code bytes)
   float* dst_scale;    // [dstN]
   float* tmp_rowmax;   // [src_rows_total + 1] scratch
   int src_rows_total;  // rows of the full tensor (per-tensor scale spans all of them)

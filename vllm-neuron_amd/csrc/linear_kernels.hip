@@ -21,6 +21,8 @@
 // Prefill (M > 16): gemm_kernel — 128 x 128 tile, x through swizzled LDS, W straight
 //   from global in fragment order.
 //
+// MXFP4 (4-bit codes + one power-of-two scale per 32 k, mi_common.h): 16 x 128 tiles; gemv_w4_kernel / gemm_w4_kernel.
+//
 // Both share one epilogue on D[n = 4g + r][m = c] (lane = 16 g + c): dequant scale, bias,
 // then fp32 store | RoPE + q/KV-pool scatter | SwiGLU.
 
@@ -214,6 +216,9 @@ template <int WD>
 __device__ __forceinline__ int xfrag_slot(int c8, int m, int M) {
   if constexpr (WD == MI_W_BF16) {
     return c8 * M + m;  // kt = c8 / 4, g = c8 % 4
+  } else if constexpr (WD == MI_W_MXFP4) {
+    const int kt = c8 >> 4, c = c8 & 15;  // k = kt*128 + g*32 + j*8 + e: chunk 4 g + j feeds MFMA j of lane group g
+    return (((kt * 4 + (c & 3)) * 4 + (c >> 2)) * M) + m;
   } else {
     const int kt = c8 >> 3, c = c8 & 7;  // k = kt*64 + g*16 + s*8 + j
     return (((kt * 2 + (c & 1)) * 4 + (c >> 1)) * M) + m;
@@ -1516,6 +1521,245 @@ static int launch_gemv_bigk_t(const LinearW& w, int M, const ProArgs& p, const E
   }
 }
 
+// =====================================================================================
+// GEMV on MXFP4 weights (4-bit block-scaled codes, mi_common.h)
+// =====================================================================================
+// One kernel for every shape, on gemv_bigk_kernel's schedule: KS waves split each K-chunk of one row-tile, a work-group
+// walks TP = up to 8 / KS row-tiles side by side against the SAME staged activation chunk, the chunk is staged in
+// MFMA-fragment order between two barriers while the next chunk's first weight batches are already in flight, K-slices are
+// summed in wave order, MG = 2 shares one weight stream between two 16-column groups (17 .. 32 rows).  What differs is the
+// balance: a 1 KiB load is a 16 x 128 tile that feeds FOUR MFMAs per column group (four 16-byte LDS operand reads, 16
+// converts) where the 1-byte formats feed two, so a batch is kW4U = 4 loads -- two batches in flight per wave are the 64
+// wave-loads a CU holds -- and the lane's four block scales of the batch travel with it as one 4-byte load.
+// The hot loop is branch-free like the others: loads are unconditional and never predicated (k-tiles past the wave's slice
+// re-request its last tile and multiply the zeroed LDS slot; their scale byte is whichever real one the index wraps to).
+// LDS: gemv_bigk_kernel's.  (it, ch, b) = (pass, chunk, batch) of the next batch to request / to multiply, advanced by
+// counting: no division on the way to a weight request.
+struct W4Seq {
+  int it = 0, ch = 0, b = 0;
+  __device__ __forceinline__ void next(int NC, int nb) {
+    if (++b == nb) { b = 0; if (++ch == NC) { ch = 0; ++it; } }
+  }
+};
+
+template <int PRO, int EPI, int MG>
+__global__ __launch_bounds__(kGemvWaves * 64) void gemv_w4_kernel(const uint4* __restrict__ W, const uint32_t* __restrict__ S,
+                                                                  int NT, int KT, int M, int K, int KS, int TP, int KTW,
+                                                                  ProArgs p, EpiArgs e) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int WD = MI_W_MXFP4, TK = 128;
+  const int CKT = KS * KTW;                                            // k-tiles of a chunk: KTW per K-slice
+  uint4* xf = reinterpret_cast<uint4*>(smem);
+  const int zero_slot = (M * CKT * TK) >> 3;
+  unsigned char* tail = smem + (size_t)M * CKT * TK * 2 + 16;
+  f32x4_t* red = reinterpret_cast<f32x4_t*>(tail);                     // [MG][8 waves][64 lanes]
+  float* sc_lds = reinterpret_cast<float*>(tail + MG * kGemvWaves * 64 * 16);   // [8 row-tiles][16]
+  float* bi_lds = sc_lds + kGemvWaves * 16;
+  float* ssq_lds = bi_lds + kGemvWaves * 16;                           // [16 MG rows][16 waves]
+
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int g = lane >> 4, c = lane & 15;
+  const int tsub = wave / KS, kslice = wave - tsub * KS;
+  const bool wave_on = tsub < TP;                                      // waves beyond KS * TP only stage activations
+  bool col_ok[MG];                                                     // column c of group q = activation row 16 q + c
+#pragma unroll
+  for (int q = 0; q < MG; ++q) col_ok[q] = 16 * q + c < M;
+  const int NC = ceil_div(KT, CKT), KQ = ceil_div(KT, kW4U);
+  const int nb = ceil_div(KTW, kW4U);                 // batches per (pass, chunk), same for every wave
+  const int units = ceil_div(NT, TP);                 // a pass = TP row-tiles
+  const int my_units = (int)blockIdx.x < units ? ceil_div(units - (int)blockIdx.x, (int)gridDim.x) : 0;
+  const int total = my_units * NC * nb;
+
+  // the K-slice of this wave inside chunk ch, clipped to the chunk and to KT
+  auto slice = [&](int ch, int& kbeg, int& kend) {
+    const int cend = min((ch + 1) * CKT, KT);
+    kbeg = min(ch * CKT + kslice * KTW, cend);
+    kend = min(kbeg + KTW, cend);
+  };
+  u32x4_t bufA[kW4U], bufB[kW4U];
+  uint32_t swA = 0, swB = 0;                          // the lane's scale words of the two batches in flight
+  W4Seq rq, mu;                                       // next batch to request / to multiply
+  auto issue = [&](u32x4_t (&buf)[kW4U], uint32_t& sw) {
+    int kbeg, kend;
+    slice(rq.ch, kbeg, kend);
+    const int tile_raw = ((int)blockIdx.x + rq.it * (int)gridDim.x) * TP + tsub;
+    const int tile = min(tile_raw, NT - 1);
+    const int klast = min(max(kend - 1, kbeg), KT - 1);
+    const bool any = rq.it < my_units && wave_on && kbeg < kend && tile_raw < NT;
+    const uint4* base = any ? W + (size_t)tile * KT * 64 + lane : W;
+    const size_t kstep = any ? 64 : 0;
+    const int kt0 = kbeg + rq.b * kW4U;
+#pragma unroll
+    for (int u = 0; u < kW4U; ++u) stream_load16(buf[u], base + (size_t)min(kt0 + u, klast) * kstep);
+    sw = __builtin_nontemporal_load(any ? S + ((size_t)tile * KQ + (min(kt0, klast) >> 2)) * 64 + lane : S);
+    rq.next(NC, nb);
+  };
+
+  if (tid == 0) xf[zero_slot] = make_uint4(0, 0, 0, 0);
+  if constexpr (MG > 1 && PRO != PRO_BF16) {   // (row-wise staging fills one wave's slot per row; the first staging barrier orders this)
+    for (int i = tid; i < MG * 16 * 16; i += blockDim.x) ssq_lds[i] = 0.f;
+  }
+  issue(bufA, swA);
+  issue(bufB, swB);
+
+  f32x4_t acc[MG];
+#pragma unroll
+  for (int q = 0; q < MG; ++q) acc[q] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  auto process = [&](u32x4_t (&buf)[kW4U], uint32_t sw) {
+    const int it = mu.it, ch = mu.ch, b = mu.b;
+    int kbeg, kend;
+    slice(ch, kbeg, kend);
+    const int tile0 = ((int)blockIdx.x + it * (int)gridDim.x) * TP;    // first row-tile of the pass
+    if (b == 0) {   // a new chunk: every wave is done with the previous image
+      __syncthreads();
+      if (ch == 0 && tid < 16 * TP) {
+        const int tile = min(tile0 + (tid >> 4), NT - 1);
+        sc_lds[tid] = e.scale[tile * 16 + (tid & 15)];
+        bi_lds[tid] = e.bias ? e.bias[tile * 16 + (tid & 15)] : 0.f;
+      }
+      const int k0 = ch * CKT * TK, ck = (min((ch + 1) * CKT, KT) - ch * CKT) * TK;
+      if constexpr (MG > 1 && PRO != PRO_BF16) {
+        if (ck <= 64 * kRowJ * 8) gemv_stage_chunk_rows<WD, PRO>(p, M, K, k0, ck, xf, ssq_lds, ch == 0, it == 0, it == 0 && blockIdx.x == 0);
+        else gemv_stage_chunk<WD, PRO>(p, M, K, k0, ck, xf, ssq_lds, ch == 0, it == 0, it == 0 && blockIdx.x == 0);
+      } else {
+        gemv_stage_chunk<WD, PRO>(p, M, K, k0, ck, xf, ssq_lds, ch == 0, it == 0, it == 0 && blockIdx.x == 0);
+      }
+      __syncthreads();
+    }
+    const int kt0 = kbeg + b * kW4U;                  // global k-tile of the batch's first load
+    const int kl0 = kt0 - ch * CKT;                   // ... and its index inside the chunk image
+#pragma unroll
+    for (int u = 0; u < kW4U; ++u) {
+      const int kt = kl0 + u;
+      const bool live = kt0 + u < kend;
+      const u32x4_t w = buf[u];
+      const float bs = e8m0_to_f32(sw, (kt0 + u) & 3);                 // 2^E of this lane's block in k-tile kt0 + u
+      bf16x8_t a[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) a[j] = decode8_fp4(w[j], bs);        // decoded once for all column groups
+#pragma unroll
+      for (int q = 0; q < MG; ++q) {
+        const bool ok = live && col_ok[q];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bf16x8_t bb = __builtin_bit_cast(bf16x8_t, xf[ok ? ((kt * 4 + j) * 4 + g) * M + 16 * q + c : zero_slot]);
+          acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[j], bb, acc[q], 0, 0, 0);
+        }
+      }
+    }
+    if (ch == NC - 1 && b == nb - 1) {   // the pass's row-tiles are done: combine the K-slices in slice order
+      if (KS > 1) {
+#pragma unroll
+        for (int q = 0; q < MG; ++q) red[(q * kGemvWaves + wave) * 64 + lane] = acc[q];
+        __syncthreads();                 // (the next write to `red` comes behind the staging barriers of the next pass)
+      }
+      const int tile = tile0 + tsub;
+      if (kslice == 0 && wave_on && tile < NT) {   // the first wave of a row-tile finishes all its column groups
+#pragma unroll
+        for (int q = 0; q < MG; ++q) {
+          if (!col_ok[q]) continue;
+          f32x4_t sum = acc[q];
+          if (KS > 1) {
+            sum = red[(q * kGemvWaves + wave) * 64 + lane];
+            for (int w = 1; w < KS; ++w) {
+              const f32x4_t t = red[(q * kGemvWaves + wave + w) * 64 + lane];
+              sum[0] += t[0]; sum[1] += t[1]; sum[2] += t[2]; sum[3] += t[3];
+            }
+          }
+          float rmul = 1.f;
+          if constexpr (PRO != PRO_BF16) rmul = gemv_row_rinv(ssq_lds, 16 * q + c, K, p.eps);
+          epilogue_lds<EPI>(e, 16 * q + c, tile * 16 + g * 4, sc_lds + tsub * 16 + g * 4, e.bias ? bi_lds + tsub * 16 + g * 4 : nullptr,
+                            sum, rmul);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < MG; ++q) acc[q] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    }
+    mu.next(NC, nb);
+  };
+  for (int i = 0; i < total; i += 2) {
+    process(bufA, swA);
+    issue(bufA, swA);
+    if (i + 1 < total) process(bufB, swB);
+    issue(bufB, swB);
+  }
+}
+
+// (KS, TP, KTW) for NT row-tiles of KT k-tiles at M rows on `slots` resident work-groups.  A K-slice is KTW k-tiles of a
+// chunk; KTW is 1, 2 or a multiple of kW4U, so that the live k-tiles of a batch lie in ONE scale word (slices start at
+// multiples of KTW, batches at multiples of kW4U inside a slice).  KS * KTW k-tiles of M rows must fit the LDS.  Fewest loads
+// issued on the busiest CU (dead ones of a ragged batch included), then the fewest staging rounds, then the most
+// streaming waves, then the smallest K split.
+struct W4Plan { int ks, tp, ktw; };
+static W4Plan gemv_w4_plan(int M, int NT, int KT, int slots) {
+  const int mg = M > 16 ? 2 : 1;
+  const int cap = (int)((160 * 1024 - gemv_bigk_fixed_lds(mg)) / ((size_t)M * 128 * 2));   // k-tiles of activations the LDS holds
+  W4Plan best{1, 1, 1};
+  long best_cost = 1L << 60, best_rounds = 1L << 60;
+  int best_waves = 0;
+  for (int ks = 1; ks <= kGemvWaves; ks *= 2) {
+    if (cap / ks < 1) break;
+    const int want = ceil_div(KT, ks), room = cap / ks;
+    int ktw = want <= 2 ? want : ceil_div(want, kW4U) * kW4U;
+    if (ktw > room) ktw = room < kW4U ? (room >= 2 ? 2 : 1) : room / kW4U * kW4U;
+    const int nc = ceil_div(KT, ks * ktw), nb = ceil_div(ktw, kW4U);
+    for (int tp = 1; tp * ks <= kGemvWaves; ++tp) {
+      const int passes = ceil_div(ceil_div(NT, tp), slots);
+      const long cost = (long)passes * nc * nb * ks * tp, rounds = (long)passes * nc;
+      const int waves = ks * tp;
+      const bool better = cost < best_cost || (cost == best_cost && (rounds < best_rounds || (rounds == best_rounds && waves > best_waves)));
+      if (better) { best = {ks, tp, ktw}; best_cost = cost; best_rounds = rounds; best_waves = waves; }
+    }
+  }
+  return best;
+}
+
+template <int PRO, int EPI, int MG>
+static int launch_gemv_w4_mg(const LinearW& w, int M, const ProArgs& p, const EpiArgs& e, hipStream_t s) {
+  int num_cu = 0;
+  MI_TRY_(device_num_cu(&num_cu));
+  const int NT = w.N / 16, KT = w.K / 128;
+  const W4Plan pl = gemv_w4_plan(M, NT, KT, num_cu);
+  const size_t lds = (size_t)M * pl.ks * pl.ktw * 128 * 2 + gemv_bigk_fixed_lds(MG);
+  MI_CHECK(lds <= 160 * 1024, "gemv_w4: activation chunk does not fit in LDS");
+  auto kern = gemv_w4_kernel<PRO, EPI, MG>;
+  MI_TRY_(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024));
+  const int units = ceil_div(NT, pl.tp);
+  int grid = units;
+  if (units > num_cu) grid = ceil_div(units, ceil_div(units, num_cu));
+  const uint4* W = reinterpret_cast<const uint4*>(w.w);
+  const uint32_t* S = reinterpret_cast<const uint32_t*>(reinterpret_cast<const unsigned char*>(w.w) + (size_t)w.N * w.K / 2);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kGemvWaves * 64), lds, s, W, S, NT, KT, M, w.K, pl.ks, pl.tp, pl.ktw, p, e);
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+template <int PRO, int EPI>
+static int launch_gemv_w4_t(const LinearW& w, int M, const ProArgs& p, const EpiArgs& e, hipStream_t s) {
+  if (M <= 16) return launch_gemv_w4_mg<PRO, EPI, 1>(w, M, p, e, s);
+  return launch_gemv_w4_mg<PRO, EPI, 2>(w, M, p, e, s);
+}
+// the (prologue, epilogue) pairs of launch_gemv_wd
+static int launch_gemv_w4(const LinearW& w, int M, int pro, const ProArgs& p, int epi, const EpiArgs& e, hipStream_t s) {
+  MI_CHECK(w.K % 128 == 0, "gemv: MXFP4 weights need K % 128 == 0");
+  if (pro == PRO_BF16) {
+    MI_CHECK(p.ldx % 8 == 0, "gemv: activation row stride must be a multiple of 8 elements");
+    if (epi == EPI_RESID) return launch_gemv_w4_t<PRO_BF16, EPI_RESID>(w, M, p, e, s);
+    if (epi == EPI_F32) return launch_gemv_w4_t<PRO_BF16, EPI_F32>(w, M, p, e, s);
+  } else if (p.partial) {
+    if (epi == EPI_QKV) return launch_gemv_w4_t<PRO_NORM_PARTIAL, EPI_QKV>(w, M, p, e, s);
+    if (epi == EPI_QKV_F8) return launch_gemv_w4_t<PRO_NORM_PARTIAL, EPI_QKV_F8>(w, M, p, e, s);
+    if (epi == EPI_SWIGLU) return launch_gemv_w4_t<PRO_NORM_PARTIAL, EPI_SWIGLU>(w, M, p, e, s);
+    if (epi == EPI_F32) return launch_gemv_w4_t<PRO_NORM_PARTIAL, EPI_F32>(w, M, p, e, s);
+  } else {
+    if (epi == EPI_QKV) return launch_gemv_w4_t<PRO_NORM, EPI_QKV>(w, M, p, e, s);
+    if (epi == EPI_QKV_F8) return launch_gemv_w4_t<PRO_NORM, EPI_QKV_F8>(w, M, p, e, s);
+    if (epi == EPI_SWIGLU) return launch_gemv_w4_t<PRO_NORM, EPI_SWIGLU>(w, M, p, e, s);
+    if (epi == EPI_F32) return launch_gemv_w4_t<PRO_NORM, EPI_F32>(w, M, p, e, s);
+  }
+  set_error("gemv: unsupported prologue / epilogue combination");
+  return MI_EINVAL;
+}
+
 // valid (prologue, epilogue) pairs: bf16 activations feed the row-parallel projections
 // (fp32 / residual out); the norm prologues feed QKV, gate|up and lm_head
 template <int WD>
@@ -1545,6 +1789,7 @@ int launch_gemv(const LinearW& w, int M, int pro, const ProArgs& p, int epi, con
     case MI_W_BF16: return launch_gemv_wd<MI_W_BF16>(w, M, pro, p, epi, e, s);
     case MI_W_F8E4M3: return launch_gemv_wd<MI_W_F8E4M3>(w, M, pro, p, epi, e, s);
     case MI_W_INT8: return launch_gemv_wd<MI_W_INT8>(w, M, pro, p, epi, e, s);
+    case MI_W_MXFP4: return launch_gemv_w4(w, M, pro, p, epi, e, s);
   }
   set_error("gemv: bad weight dtype");
   return MI_EINVAL;
@@ -1968,7 +2213,7 @@ static int launch_gemm_wide_wd(const LinearW& w, int T, const uint16_t* x, int l
 }
 // the wide tile needs 1-byte weights
 static bool gemm_wide_wanted(const LinearW& w, int T, size_t ws_bytes) {
-  if (w.wd == MI_W_BF16 || w.K % 64 != 0 || (w.N / 16) < 2) return false;
+  if (w.wd == MI_W_BF16 || w.wd == MI_W_MXFP4 || w.K % 64 != 0 || (w.N / 16) < 2) return false;
   const int mode = gemm_wide_mode();
   if (mode == 1) return true;
   if (mode == 0) return false;
@@ -1978,16 +2223,160 @@ static bool gemm_wide_wanted(const LinearW& w, int T, size_t ws_bytes) {
 int launch_gemm_wide(const LinearW& w, int T, const uint16_t* x, int ldx, int epi, const EpiArgs& e, hipStream_t s,
                      float* splitk_ws, size_t splitk_ws_bytes, SlabSum* defer, int force_bm, int force_ks) {
   if (defer) *defer = SlabSum();
-  MI_CHECK(w.wd != MI_W_BF16 && w.K % 64 == 0 && ldx % 8 == 0, "gemm_wide: 1-byte weights, K % 64 == 0");
+  MI_CHECK((w.wd == MI_W_F8E4M3 || w.wd == MI_W_INT8) && w.K % 64 == 0 && ldx % 8 == 0, "gemm_wide: 1-byte weights, K % 64 == 0");
   if (w.wd == MI_W_F8E4M3)
     return launch_gemm_wide_wd<MI_W_F8E4M3>(w, T, x, ldx, epi, e, s, splitk_ws, splitk_ws_bytes, defer, force_bm, force_ks);
   return launch_gemm_wide_wd<MI_W_INT8>(w, T, x, ldx, epi, e, s, splitk_ws, splitk_ws_bytes, defer, force_bm, force_ks);
+}
+
+// =====================================================================================
+// GEMM on MXFP4 weights (context encoding)
+// =====================================================================================
+// gemm_kernel's sibling: 128 (n) x 128 (m) work-group tile, 4 waves as 2 x 2, each 64 x 64.  The K-step is 128 = ONE weight
+// tile per 16 rows: a wave's four tiles (4 KiB of codes + four scale words) are decoded once per K-step into their four A
+// fragments each (16 MFMA operands, 64 registers) while the raw registers refill with the next K-step's tiles.  The activation
+// tile [128 m][128 k] bf16 goes through 32 KiB of LDS, 16 chunks of 16 bytes per 256-byte row.
+// Swizzle.  Lane (g, c) reads row 16 t + c, chunk 4 g + j for MFMA j.  A row is exactly the 64 banks, so the 16-byte bank slot
+// of a read is chunk ^ key(row) alone.  A ds_read_b128 is serviced in groups of 16 lanes made of 8 columns of one lane group
+// and the other 8 columns of its neighbour: {g = 0: c in A, g = 1: c in B}, {g = 0: B, g = 1: A}, and the same for g = 2, 3,
+// with A = {0-3, 12-15}, B = {4-11} (xs_swz above).  key(c) = c ^ 4 for c in B, c for c in A maps both halves onto A, so a
+// group's slots are (4 g + j) ^ A and (4 (g ^ 1) + j) ^ A = (4 g + j) ^ B: all 16 different, for every j and both pairings
+// (enumerated).  The staging stores of a row (16 lanes, chunk sch) land on sch ^ key: a permutation, conflict-free as well.
+__device__ __forceinline__ int xs4_swz(int r) { return (r & 15) ^ ((((r >> 2) ^ (r >> 3)) & 1) << 2); }
+
+template <int EPI, bool SPLIT>
+__global__ __launch_bounds__(256) void gemm_w4_kernel(const uint4* __restrict__ W, const uint32_t* __restrict__ S, int NT, int KT,
+                                                      int T, const uint16_t* __restrict__ x, int ldx, EpiArgs e,
+                                                      float* __restrict__ slab) {
+  __shared__ __attribute__((aligned(16))) uint4 xs[kBM * 16];  // 32 KiB
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int g = lane >> 4, c = lane & 15;
+  const int wn = wave >> 1, wm = wave & 1;
+  // XCD-aware tile order (see gemm_a8_kernel)
+  const int mtiles = ceil_div(T, kBM), ntiles = ceil_div(NT, kBN / 16);
+  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
+  const int mblk = seq % mtiles, nblk = (seq / mtiles) * 8 + xcd;
+  if (nblk >= ntiles) return;
+  const int m0 = mblk * kBM, nt0 = nblk * (kBN / 16) + wn * 4;
+  const int KQ = ceil_div(KT, kW4U);
+  const int ks_per = SPLIT ? ceil_div(KT, (int)gridDim.z) : KT;   // a K-step is a k-tile
+  const int ks_beg = SPLIT ? (int)blockIdx.z * ks_per : 0;
+  const int nks = min(ks_beg + ks_per, KT);
+
+  f32x4_t acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  // x staging: thread -> rows (tid / 16 + 16 i), 16-byte chunk tid % 16
+  const int srow = tid >> 4, sch = tid & 15;
+  u32x4_t xr[8], wr[4];
+  uint32_t sw[4];
+  auto load_x = [&](int ks) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int m = min(m0 + srow + 16 * i, T - 1);   // rows past T: a copy of the last row, never stored
+      xr[i] = *reinterpret_cast<const u32x4_t*>(x + (size_t)m * ldx + ks * 128 + sch * 8);
+    }
+  };
+  auto load_w = [&](int ks) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int nt = min(nt0 + i, NT - 1);
+      wr[i] = *reinterpret_cast<const u32x4_t*>(W + ((size_t)nt * KT + ks) * 64 + lane);
+      sw[i] = S[((size_t)nt * KQ + (ks >> 2)) * 64 + lane];
+    }
+  };
+
+  if (ks_beg < nks) {
+    load_x(ks_beg);
+    load_w(ks_beg);
+  }
+  for (int ks = ks_beg; ks < nks; ++ks) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int r = srow + 16 * i;
+      *reinterpret_cast<u32x4_t*>(&xs[r * 16 + (sch ^ xs4_swz(r))]) = xr[i];
+    }
+    bf16x8_t a[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float bs = e8m0_to_f32(sw[i], ks & 3);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) a[i][j] = decode8_fp4(wr[i][j], bs);
+    }
+    __syncthreads();
+    if (ks + 1 < nks) {      // the raw registers are free again: next K-step's operands
+      load_x(ks + 1);
+      load_w(ks + 1);
+    }
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      const int r = wm * 64 + mt * 16 + c;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bf16x8_t b = __builtin_bit_cast(bf16x8_t, xs[r * 16 + ((4 * g + j) ^ xs4_swz(r))]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][j], b, acc[i][mt], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (nt0 + i >= NT) continue;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      const int m = m0 + wm * 64 + mt * 16 + c;
+      if (m >= T) continue;
+      const int n0 = (nt0 + i) * 16 + g * 4;
+      if constexpr (SPLIT) {
+        *reinterpret_cast<float4*>(slab + ((size_t)blockIdx.z * T + m) * (NT * 16) + n0) =
+            make_float4(acc[i][mt][0], acc[i][mt][1], acc[i][mt][2], acc[i][mt][3]);
+      } else {
+        epilogue<EPI>(e, m, n0, acc[i][mt]);
+      }
+    }
+  }
+}
+
+static int launch_gemm_w4(const LinearW& w, int T, const uint16_t* x, int ldx, int epi, const EpiArgs& e, hipStream_t s,
+                          float* splitk_ws, size_t splitk_ws_bytes, SlabSum* defer) {
+  MI_CHECK(w.N % 16 == 0 && w.K % 128 == 0, "gemm: MXFP4 weights need N % 16 == 0 and K % 128 == 0");
+  MI_CHECK(ldx % 8 == 0, "gemm: x row stride must be a multiple of 8 elements");
+  const int NT = w.N / 16, KT = w.K / 128;
+  const int mtiles = ceil_div(T, kBM), ntiles = ceil_div(w.N, kBN);
+  const int KS = gemm_pick_splitk(mtiles * ntiles, KT, T, w.N, splitk_ws ? splitk_ws_bytes : 0);
+  dim3 grid(8 * mtiles * ceil_div(ntiles, 8), 1, KS);
+  const uint4* W = reinterpret_cast<const uint4*>(w.w);
+  const uint32_t* S = reinterpret_cast<const uint32_t*>(reinterpret_cast<const unsigned char*>(w.w) + (size_t)w.N * w.K / 2);
+#define MI_G4(EPI_) \
+  do { \
+    if (KS == 1) { \
+      hipLaunchKernelGGL((gemm_w4_kernel<EPI_, false>), grid, dim3(256), 0, s, W, S, NT, KT, T, x, ldx, e, nullptr); \
+    } else { \
+      hipLaunchKernelGGL((gemm_w4_kernel<EPI_, true>), grid, dim3(256), 0, s, W, S, NT, KT, T, x, ldx, e, splitk_ws); \
+      if (defer && EPI_ == EPI_RESID) { *defer = SlabSum{splitk_ws, KS, T, w.N, e.scale, e.bias, e.row_scale}; } \
+      else hipLaunchKernelGGL((splitk_reduce_kernel<EPI_>), dim3(ceil_div(T * (w.N / 4), 256)), dim3(256), 0, s, splitk_ws, KS, T, w.N, e); \
+    } \
+  } while (0)
+  if (epi == EPI_QKV) MI_G4(EPI_QKV);
+  else if (epi == EPI_QKV_F8) MI_G4(EPI_QKV_F8);
+  else if (epi == EPI_SWIGLU) MI_G4(EPI_SWIGLU);
+  else if (epi == EPI_RESID) MI_G4(EPI_RESID);
+  else MI_G4(EPI_F32);
+#undef MI_G4
+  MI_HIP(hipGetLastError());
+  return MI_OK;
 }
 
 int launch_gemm(const LinearW& w, int T, const uint16_t* x, int ldx, int epi, const EpiArgs& e, hipStream_t s,
                 float* splitk_ws, size_t splitk_ws_bytes, SlabSum* defer) {
   if (defer) *defer = SlabSum();
   MI_CHECK(T >= 1, "gemm: T must be >= 1");
+  if (w.wd == MI_W_MXFP4) return launch_gemm_w4(w, T, x, ldx, epi, e, s, splitk_ws, splitk_ws_bytes, defer);
   if (gemm_wide_wanted(w, T, splitk_ws ? splitk_ws_bytes : 0) && ldx % 8 == 0)
     return launch_gemm_wide(w, T, x, ldx, epi, e, s, splitk_ws, splitk_ws_bytes, defer);
   MI_CHECK(w.N % 16 == 0 && w.K % 64 == 0, "gemm: N % 16 == 0 and K % 64 == 0 required");
@@ -2723,6 +3112,30 @@ __device__ __forceinline__ int dst_to_src_row(const QuantJob& j, int r) {
   return i < j.n_rows ? i : -1;
 }
 
+// MXFP4, the rule of mi_common.h on one block: 32 consecutive weights of a row -> 16 code bytes (even k in the low nibble)
+// and the e8m0 scale byte.  Plain float / integer code: the exponent comes from the bits of amax, the codes from the seven
+// midpoints of the e2m1 grid with the tie going to the even code.
+__device__ __forceinline__ uint32_t quant_block_mxfp4(const float* __restrict__ src, uint4& out) {
+  float v[32], amax = 0.f;
+#pragma unroll
+  for (int k = 0; k < 32; ++k) { v[k] = src[k]; amax = fmaxf(amax, fabsf(v[k])); }
+  int E = 0;
+  if (amax > 0.f) E = min(max((int)((__builtin_bit_cast(uint32_t, amax) >> 23) & 0xffu) - 127 - 2, -100), 100);   // floor(log2(amax)) - 2; subnormal amax: -100
+  const float inv = __builtin_bit_cast(float, (uint32_t)(127 - E) << 23);   // 2^-E, exact
+  uint32_t o[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int k = 0; k < 32; ++k) {
+    const float t = v[k] * inv, a = fabsf(t);
+    uint32_t code = (a > 0.25f) + (a >= 0.75f) + (a > 1.25f) + (a >= 1.75f) + (a > 2.5f) + (a >= 3.5f) + (a > 5.0f);
+    if (v[k] < 0.f) code |= 8u;
+    if (t != t) code = 7u;          // NaN -> +6
+    if (!(amax > 0.f)) code = 0u;
+    o[k >> 3] |= code << (4 * (k & 7));
+  }
+  out = make_uint4(o[0], o[1], o[2], o[3]);
+  return (uint32_t)(E + 127);
+}
+
 // one wave per destination tile
 template <int WD>
 __global__ __launch_bounds__(256) void quant_tile_kernel(QuantJob j, int nt_lo, int nt_cnt, int KT) {
@@ -2732,15 +3145,24 @@ __global__ __launch_bounds__(256) void quant_tile_kernel(QuantJob j, int nt_lo, 
   const int r = nt * 16 + (lane & 15), gq = lane >> 4;
   const int i = dst_to_src_row(j, r);
   if (i < 0) return;
-  constexpr int EPL = (WD == MI_W_BF16) ? 8 : 16;  // elements per lane
+  constexpr int EPL = (WD == MI_W_BF16) ? 8 : (WD == MI_W_MXFP4 ? 32 : 16);  // elements per lane
   const int col0 = kt * (EPL * 4) + gq * EPL;      // first of the lane's columns, relative to src_col0
   const bool pad_row = i >= j.n_rows - j.pad_rows;
   const int k_src = j.K - j.pad_cols;
+  // MXFP4: the lane's scale byte in the plane behind the code tiles (mi_common.h); the last k-tile also fills its word's tail with 2^0
+  auto put_block_scale = [&](uint32_t byte) {
+    unsigned char* sp = reinterpret_cast<unsigned char*>(j.dst) + (size_t)j.dst_rows * j.K / 2 +
+                        (((size_t)nt * ceil_div(KT, kW4U) + (kt >> 2)) * 64 + lane) * 4;
+    sp[kt & 3] = (unsigned char)byte;
+    if (kt == KT - 1)
+      for (int u = (kt & 3) + 1; u < 4; ++u) sp[u] = 127;
+  };
   if (pad_row || col0 >= k_src) {                  // EPL divides every head size: a lane is all padding or none
     if (pad_row && kt == 0 && gq == 0) j.dst_scale[r] = 1.f;
+    if constexpr (WD == MI_W_MXFP4) put_block_scale(127);
     if (!pad_row && kt == 0 && gq == 0) {
       float sc = 1.f;
-      if constexpr (WD != MI_W_BF16) {
+      if constexpr (WD == MI_W_F8E4M3 || WD == MI_W_INT8) {
         const float qm = (WD == MI_W_INT8) ? 127.f : 448.f;
         const float am = (j.quant_type == MI_Q_PER_TENSOR_SYMMETRIC) ? j.tmp_rowmax[j.src_rows_total] : j.tmp_rowmax[j.src_row0 + i];
         sc = am > 0.f ? am / qm : 1.f;
@@ -2753,7 +3175,7 @@ __global__ __launch_bounds__(256) void quant_tile_kernel(QuantJob j, int nt_lo, 
   const int srow = j.src_row0 + i;
   const float* src = j.src + (size_t)srow * j.ld + j.src_col0 + col0;
   float scale = 1.f;
-  if constexpr (WD != MI_W_BF16) {
+  if constexpr (WD == MI_W_F8E4M3 || WD == MI_W_INT8) {
     const float qmax = (WD == MI_W_INT8) ? 127.f : 448.f;
     const float amax = (j.quant_type == MI_Q_PER_TENSOR_SYMMETRIC) ? j.tmp_rowmax[j.src_rows_total] : j.tmp_rowmax[srow];
     scale = amax > 0.f ? amax / qmax : 1.f;
@@ -2765,6 +3187,8 @@ __global__ __launch_bounds__(256) void quant_tile_kernel(QuantJob j, int nt_lo, 
 #pragma unroll
     for (int k = 0; k < 4; ++k) o[k] = pack_bf16x2(src[2 * k], src[2 * k + 1]);
     out = make_uint4(o[0], o[1], o[2], o[3]);
+  } else if constexpr (WD == MI_W_MXFP4) {
+    put_block_scale(quant_block_mxfp4(src, out));
   } else {
     const float qmax = (WD == MI_W_INT8) ? 127.f : 448.f;
     uint32_t o[4] = {0, 0, 0, 0};
@@ -2784,7 +3208,9 @@ __global__ __launch_bounds__(256) void quant_tile_kernel(QuantJob j, int nt_lo, 
 
 int run_quant_job(const QuantJob& j, hipStream_t s) {
   MI_CHECK(j.K % 64 == 0, "quantize: K % 64 == 0 required");
-  if (j.wd != MI_W_BF16) {
+  MI_CHECK(j.wd != MI_W_MXFP4 || (j.K % 128 == 0 && j.dst_rows % 16 == 0 && j.dst_rows > 0),
+           "quantize: MXFP4 needs K % 128 == 0 and N % 16 == 0");
+  if (j.wd == MI_W_F8E4M3 || j.wd == MI_W_INT8) {
     hipLaunchKernelGGL(rowmax_kernel, dim3(j.src_rows_total), dim3(256), 0, s, j.src, j.ld, j.tmp_rowmax);
     hipLaunchKernelGGL(allmax_kernel, dim3(1), dim3(256), 0, s, j.tmp_rowmax, j.src_rows_total, j.tmp_rowmax + j.src_rows_total);
   }
@@ -2796,6 +3222,7 @@ int run_quant_job(const QuantJob& j, hipStream_t s) {
   const dim3 grid(ceil_div(waves, 4)), block(256);
   if (j.wd == MI_W_BF16) hipLaunchKernelGGL((quant_tile_kernel<MI_W_BF16>), grid, block, 0, s, j, nt_lo, nt_hi - nt_lo, KT);
   else if (j.wd == MI_W_F8E4M3) hipLaunchKernelGGL((quant_tile_kernel<MI_W_F8E4M3>), grid, block, 0, s, j, nt_lo, nt_hi - nt_lo, KT);
+  else if (j.wd == MI_W_MXFP4) hipLaunchKernelGGL((quant_tile_kernel<MI_W_MXFP4>), grid, block, 0, s, j, nt_lo, nt_hi - nt_lo, KT);
   else hipLaunchKernelGGL((quant_tile_kernel<MI_W_INT8>), grid, block, 0, s, j, nt_lo, nt_hi - nt_lo, KT);
   MI_HIP(hipGetLastError());
   return MI_OK;
@@ -2813,11 +3240,30 @@ __global__ void untile_kernel(const uint4* __restrict__ tiled, int NT, int KT, i
   *reinterpret_cast<uint4*>(out + (size_t)r * K * eb + byte_col) = v;
 }
 
+// MXFP4: N K / 2 code bytes row-major (even k in the low nibble), then N K / 32 scale bytes row-major [N, K / 32]
+__global__ void untile_w4_kernel(const uint4* __restrict__ tiled, int NT, int KT, int K, unsigned char* __restrict__ out) {
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  if (wave >= NT * KT) return;
+  const int nt = wave / KT, kt = wave % KT;
+  const int r = nt * 16 + (lane & 15), g = lane >> 4;
+  *reinterpret_cast<uint4*>(out + (size_t)r * (K / 2) + (size_t)kt * 64 + g * 16) = tiled[(size_t)wave * 64 + lane];
+  const unsigned char* plane = reinterpret_cast<const unsigned char*>(tiled) + (size_t)NT * 16 * K / 2;
+  out[(size_t)NT * 16 * K / 2 + (size_t)r * (K / 32) + kt * 4 + g] =
+      plane[(((size_t)nt * ceil_div(KT, kW4U) + (kt >> 2)) * 64 + lane) * 4 + (kt & 3)];
+}
+
 int launch_untile(const void* tiled, int N, int K, int wd, void* out, hipStream_t s) {
   MI_CHECK(N % 16 == 0 && K % 64 == 0, "untile: N % 16 == 0 and K % 64 == 0 required");
   const int NT = N / 16, KT = K / tile_k(wd);
+  if (wd == MI_W_MXFP4) {
+    MI_CHECK(K % 128 == 0, "untile: MXFP4 needs K % 128 == 0");
+    hipLaunchKernelGGL(untile_w4_kernel, dim3(ceil_div(NT * KT, 4)), dim3(256), 0, s, reinterpret_cast<const uint4*>(tiled), NT, KT,
+                       K, reinterpret_cast<unsigned char*>(out));
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+  }
   hipLaunchKernelGGL(untile_kernel, dim3(ceil_div(NT * KT, 4)), dim3(256), 0, s,
-                     reinterpret_cast<const uint4*>(tiled), NT, KT, K, elem_bytes(wd), reinterpret_cast<unsigned char*>(out));
+                     reinterpret_cast<const uint4*>(tiled), NT, KT, K, wd == MI_W_BF16 ? 2 : 1, reinterpret_cast<unsigned char*>(out));
   MI_HIP(hipGetLastError());
   return MI_OK;
 }

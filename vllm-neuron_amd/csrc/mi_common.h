@@ -84,6 +84,20 @@ __device__ __forceinline__ bf16x8_t decode8<MI_W_INT8>(uint32_t lo, uint32_t hi)
   return u.v;
 }
 
+// MXFP4: the four dwords of a lane's 16 bytes -> the four MFMA operands of a 128-k tile; scale = 2^E of the lane's block
+__device__ __forceinline__ bf16x8_t decode8_fp4(uint32_t w, float scale) {
+  union { bf16x2_t p[4]; bf16x8_t v; } u;
+  u.p[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0);
+  u.p[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1);
+  u.p[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2);
+  u.p[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3);
+  return u.v;
+}
+// e8m0 scale byte u (0..3) of a scale word -> 2^E as fp32
+__device__ __forceinline__ float e8m0_to_f32(uint32_t word, int u) {
+  return __builtin_bit_cast(float, ((word >> (8 * u)) & 0xffu) << 23);
+}
+
 // ---- cross-lane sums inside an aligned group of 8 or 16 lanes (DPP, no LDS) ------------
 template <int CTRL>
 __device__ __forceinline__ float dpp_add(float v) {
@@ -202,7 +216,26 @@ int ensure_dynamic_lds(const void* kernel, int bytes);        // hipFuncSetAttri
 
 // weight tile geometry: a tile is 16 rows x TILE_K(wd) columns = 1 KiB, lane l owns
 // row (l & 15), k-chunk (l >> 4) of 16 bytes.
-__host__ __device__ __forceinline__ int tile_k(int wd) { return wd == MI_W_BF16 ? 32 : 64; }
-__host__ __device__ __forceinline__ int elem_bytes(int wd) { return wd == MI_W_BF16 ? 2 : 1; }
+//
+// MI_W_MXFP4 (OCP microscaling, e2m1 codes with one e8m0 scale per 32 consecutive k of a row): 16 bytes of 4-bit codes are
+// 32 weights = one MX block, so a tile is 16 rows x 128 k and a lane needs ONE scale per tile.  In the lane's 16 bytes,
+// dword j, byte b, low / high nibble hold k = 128 kt + 32 g + 8 j + 2 b + {0, 1} (g = l >> 4): the bytes are the block's
+// codes in k order, even k in the low nibble, and cvt_scalef32_pk_bf16_fp4(dword j, scale, byte b) fills MFMA operand j.
+// The rule (the one statement besides include/mi355x_vllm.h; quant_tile_kernel implements it):
+//   amax = max |w| of the block;  amax == 0: E = 0, codes 0;  else E = clamp(floor(log2(amax)) - 2, -100, 100);
+//   scale byte = E + 127;  code = sign(w < 0) | rne_sat_e2m1(|w| * 2^-E)  (grid 0 .5 1 1.5 2 3 4 6, ties to the even
+//   code, >= 6 saturates, NaN -> +6);  value = e2m1(code) * 2^E  -- always a normal bf16, exactly.
+// Scale plane, behind the NT x KT code tiles in the same allocation: [NT][KQ = ceil(KT / 4)][64 lanes][4 bytes]; byte u of
+// lane l's word is the scale of row (l & 15), block g = l >> 4 of k-tile 4 kq + u (bytes past KT hold 127 = 2^0).  A lane
+// fetches the scales of the kW4U = 4 k-tiles of a weight batch in one coalesced 4-byte load (256 B per wave); a batch
+// never straddles a word because K-slices start at multiples of min(slice, 4) k-tiles (gemv_w4_plan).
+constexpr int kW4U = 4;   // k-tiles per scale word = 1 KiB loads per MXFP4 weight batch
+__host__ __device__ __forceinline__ int tile_k(int wd) { return wd == MI_W_BF16 ? 32 : (wd == MI_W_MXFP4 ? 128 : 64); }
+// bytes of the tiled image of an [N, K] matrix; MXFP4: N K / 2 code bytes + the scale plane, N K / 32 bytes when
+// K % 512 == 0, else padded to whole words (N * ceil(K / 512) * 16)
+__host__ __device__ __forceinline__ size_t weight_image_bytes(int N, int K, int wd) {
+  if (wd == MI_W_MXFP4) return (size_t)N * K / 2 + (size_t)N * ((K / 128 + kW4U - 1) / kW4U) * 16;
+  return (size_t)N * K * (wd == MI_W_BF16 ? 2 : 1);
+}
 
 }  // namespace mi

@@ -60,6 +60,7 @@ int dmalloc(T** p, size_t n, size_t* tally = nullptr) {
 int alloc_linear(mi_ctx* c, Linear& L, int N, int K, int wd, bool bias) {
   L.N = N; L.K = K; L.wd = wd;
   MI_CHECK(N % 16 == 0 && K % 64 == 0, "linear dims: N % 16 == 0 and K % 64 == 0 required (per TP shard)");
+  MI_CHECK(wd != MI_W_MXFP4 || K % 128 == 0, "linear dims: MXFP4 weights need K % 128 == 0 in every projection (hidden, heads x head_dim, intermediate)");
   MI_HIP(hipMalloc(&L.w, L.bytes()));
   c->weight_bytes += L.bytes();
   MI_TRY(dmalloc(&L.scale, (size_t)N, &c->weight_bytes));
@@ -504,7 +505,7 @@ int place_matrix(mi_ctx* c, Linear& L, const float* src, int rows_total, int ld,
   j.pad_rows = pad_rows; j.pad_cols = pad_cols;
   j.src = src; j.ld = ld; j.src_row0 = src_row0; j.src_col0 = src_col0; j.n_rows = n_rows; j.K = L.K;
   j.rowmap = rowmap; j.hd = c->hd; j.dst_row0 = dst_row0; j.wd = L.wd; j.quant_type = c->cfg.quant_type;
-  j.dst = L.w; j.dst_scale = L.scale; j.tmp_rowmax = c->rowmax; j.src_rows_total = rows_total;
+  j.dst = L.w; j.dst_rows = L.N; j.dst_scale = L.scale; j.tmp_rowmax = c->rowmax; j.src_rows_total = rows_total;
   return run_quant_job(j, c->stream);
 }
 
@@ -654,7 +655,7 @@ int capture_or_launch_decode(mi_ctx* c, int B, int MB) {
 extern "C" {
 
 const char* mi_last_error(void) { return mi::g_err.c_str(); }
-int mi_version(void) { return 9; }   // 9: + prefill_int8_activations, mi_op_qlinear_a8_i8 (INT8 x INT8 context-encoding GEMM); 8: + sliding_window, mi_op_paged_attn_decode_sw / mi_op_paged_attn_prefill_sw (Mistral); 7: + qk_norm, mi_op_qk_norm_rope_kv (Qwen3); 6: + mi_op_paged_attn_prefill_f8; 5: + kv_cache_dtype, mi_op_kv_write_f8 / mi_op_paged_attn_decode_f8 / mi_op_kv_dequant_gather; 4: + mi_tp_plan, mi_tp_info; 3: + in-process tensor parallelism (tp_rank = MI_TP_ALL_RANKS, tp_device_ids, tp_transport)
+int mi_version(void) { return 10; }   // 10: + MI_W_MXFP4 (4-bit block-scaled weights: gemv_w4_kernel, gemm_w4_kernel); 9: + prefill_int8_activations, mi_op_qlinear_a8_i8 (INT8 x INT8 context-encoding GEMM); 8: + sliding_window, mi_op_paged_attn_decode_sw / mi_op_paged_attn_prefill_sw (Mistral); 7: + qk_norm, mi_op_qk_norm_rope_kv (Qwen3); 6: + mi_op_paged_attn_prefill_f8; 5: + kv_cache_dtype, mi_op_kv_write_f8 / mi_op_paged_attn_decode_f8 / mi_op_kv_dequant_gather; 4: + mi_tp_plan, mi_tp_info; 3: + in-process tensor parallelism (tp_rank = MI_TP_ALL_RANKS, tp_device_ids, tp_transport)
 
 int mi_tp_plan(const mi_model_config* cfg, int32_t rank, mi_tp_plan_t* out) {
   MI_CHECK(cfg && out, "null argument");
@@ -693,6 +694,7 @@ int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out) {
   const mi_model_config& k = *cfg;
   MI_CHECK(k.num_layers > 0 && k.hidden_size > 0 && k.num_heads > 0 && k.num_kv_heads > 0, "bad geometry");
   MI_CHECK(k.head_dim == 64 || k.head_dim == 128, "head_dim must be 64 or 128");
+  MI_CHECK(k.weight_dtype != MI_W_MXFP4 || k.tp_degree <= 1, "MXFP4 weights: tp_degree > 1 is not supported (the images are not sharded)");
   if (k.tp_rank == MI_TP_ALL_RANKS && k.tp_degree > 1) {   // every rank shard inside this process (tp_group.h)
     mi_ctx* f = new mi_ctx();
     f->cfg = k;
@@ -718,7 +720,7 @@ int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out) {
   MI_CHECK(k.max_model_len >= 1, "max_model_len");
   MI_CHECK(ceil_div(k.max_model_len, k.block_size) <= kPrefillMaxBlocks,
            "max_model_len spans more than 4096 blocks per sequence: raise block_size (context encoding stages a sequence's block table in LDS)");
-  MI_CHECK(k.weight_dtype >= MI_W_BF16 && k.weight_dtype <= MI_W_INT8, "weight_dtype");
+  MI_CHECK(k.weight_dtype >= MI_W_BF16 && k.weight_dtype <= MI_W_MXFP4, "weight_dtype");
   MI_CHECK(k.quant_type == MI_Q_PER_TENSOR_SYMMETRIC || k.quant_type == MI_Q_PER_CHANNEL_SYMMETRIC, "quant_type");
   MI_CHECK(k.kv_cache_dtype == MI_KV_BF16 || k.kv_cache_dtype == MI_KV_F8E4M3, "kv_cache_dtype");
   MI_CHECK(k.qk_norm == 0 || k.qk_norm == 1, "qk_norm");
@@ -920,13 +922,14 @@ struct ArtifactHeader {
   int32_t qk_norm;          // (layout version 2) the images hold the per-head q / k norm gains
 };
 constexpr int32_t kArtifactVersion = 2, kTileFormat = 1;
+constexpr int32_t kTileFormatMxfp4 = 2;   // images of an MI_W_MXFP4 context: 16 x 128 code tiles + scale plane (mi_common.h)
 
 void make_header(const mi_ctx* c, ArtifactHeader& h) {
   const mi_model_config& k = c->cfg;
   h = ArtifactHeader{};
   memcpy(h.magic, "MI355XW", 8);
   h.version = kArtifactVersion;
-  h.tile_format = kTileFormat;
+  h.tile_format = k.weight_dtype == MI_W_MXFP4 ? kTileFormatMxfp4 : kTileFormat;
   const int32_t g[9] = {k.num_layers, k.hidden_size, k.num_heads, k.num_kv_heads, k.head_dim, k.intermediate_size,
                         k.vocab_size, k.qkv_bias, k.tie_word_embeddings};
   memcpy(h.geo, g, sizeof g);
@@ -1864,11 +1867,13 @@ int mi_op_quantize_weight(const float* w, int32_t N, int32_t K, int32_t wd, int3
                           float* scale_out, void* stream) {
   MI_CHECK(w && tiled_out && scale_out, "null argument");
   MI_CHECK(N % 16 == 0 && K % 64 == 0, "N % 16 == 0 and K % 64 == 0 required");
+  MI_CHECK(wd >= MI_W_BF16 && wd <= MI_W_MXFP4, "weight_dtype");
+  MI_CHECK(wd != MI_W_MXFP4 || K % 128 == 0, "MXFP4 weights: K % 128 == 0 required");
   float* rowmax = nullptr;
   MI_HIP(hipMalloc(reinterpret_cast<void**>(&rowmax), ((size_t)N + 16) * 4));
   QuantJob j{};
   j.src = w; j.ld = K; j.src_row0 = 0; j.src_col0 = 0; j.n_rows = N; j.K = K; j.rowmap = ROWMAP_PLAIN; j.hd = 0;
-  j.dst_row0 = 0; j.wd = wd; j.quant_type = qt; j.dst = tiled_out; j.dst_scale = scale_out; j.tmp_rowmax = rowmax;
+  j.dst_row0 = 0; j.wd = wd; j.quant_type = qt; j.dst = tiled_out; j.dst_rows = N; j.dst_scale = scale_out; j.tmp_rowmax = rowmax;
   j.src_rows_total = N;
   int rc = run_quant_job(j, (hipStream_t)stream);
   hipStreamSynchronize((hipStream_t)stream);
@@ -1883,6 +1888,10 @@ int mi_op_qlinear(const void* x, int32_t M, const void* w_tiled, const float* sc
                   int32_t K, int32_t wd, float* y, int32_t force_path, void* stream) {
   MI_CHECK(x && w_tiled && scale && y, "null argument");
   LinearW W{w_tiled, N, K, wd};
+  if (wd == MI_W_MXFP4) {
+    MI_CHECK(N % 16 == 0 && K % 128 == 0, "qlinear: MXFP4 weights need N % 16 == 0 and K % 128 == 0");
+    MI_CHECK(force_path >= 0 && force_path <= 2, "qlinear: MXFP4 weights take force_path 0, 1 or 2 (no wide-N GEMM)");
+  }
   EpiArgs e{};
   e.scale = scale; e.bias = bias; e.out_f32 = y; e.ld_out = N;
   ProArgs p{};

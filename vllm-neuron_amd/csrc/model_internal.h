@@ -17,7 +17,7 @@ struct Linear {
   float* bias = nullptr;
   int N = 0, K = 0, wd = MI_W_BF16;
   LinearW view() const { return LinearW{w, N, K, wd}; }
-  size_t bytes() const { return (size_t)N * K * elem_bytes(wd); }
+  size_t bytes() const { return weight_image_bytes(N, K, wd); }
 };
 
 struct LayerW {

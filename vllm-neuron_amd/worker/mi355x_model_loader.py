@@ -42,7 +42,8 @@ from .constants import (MI355X_MULTI_MODAL_MODELS, SUPPORTED_ARCHITECTURES,
 logger = logging.getLogger(__name__)
 
 OVERRIDE_KEYS = ("override_mi355x_config", "override_neuron_config")
-_QUANT_DTYPES = {"int8": 2, "f8e4m3": 1, "fp8": 1, "float8_e4m3fn": 1}
+# "mxfp4": OCP microscaling FP4 (e2m1 codes, one e8m0 scale per 32 K; quantization_type is ignored; tp_degree 1 only)
+_QUANT_DTYPES = {"int8": 2, "f8e4m3": 1, "fp8": 1, "float8_e4m3fn": 1, "mxfp4": 3}
 _QUANT_TYPES = {"per_tensor_symmetric": 0, "per_channel_symmetric": 1}
 
 
