@@ -45,15 +45,16 @@ extern "C" {
 enum { MI_F32 = 0, MI_BF16 = 1, MI_F8E4M3 = 2, MI_I8 = 3, MI_I64 = 4, MI_I32 = 5 };
 /* weight storage dtypes ("quantization_dtype", loader.py:895-896) */
 enum { MI_W_BF16 = 0, MI_W_F8E4M3 = 1, MI_W_INT8 = 2, MI_W_MXFP4 = 3 };
-/* MI_W_MXFP4 (ABI 10): OCP microscaling FP4, weight-only.  Blocks are 32 consecutive K elements of one output row; K % 128 == 0
+/* MI_W_MXFP4 (ABI 10): OCP microscaling FP4.  Blocks are 32 consecutive K elements of one output row; K % 128 == 0
  * and N % 16 == 0 are required (else MI_EINVAL).  Per block: amax = max |w|; amax == 0: E = 0 and all codes 0; otherwise
  * E = clamp(floor(log2(amax)) - 2, -100, 100).  The scale byte is E + 127 (e8m0).  code = sign | e2m1_rne_sat(|w| * 2^-E) on the
  * grid 0, 0.5, 1, 1.5, 2, 3, 4, 6: round to nearest, ties to the even code, magnitudes >= 6 saturate to 6, sign bit set for
  * w < 0, a NaN becomes +6.  value = e2m1(code) * 2^E, which the clamp on E keeps a normal bf16: like FP8 and INT8 the format
- * is decoded exactly and multiplied on the bf16 matrix core with fp32 accumulation.  quant_type is accepted and ignored; the
+ * is decoded exactly and multiplied on the bf16 matrix core with fp32 accumulation (weight-only; context encoding with
+ * prefill_fp8_activations = 1, ABI 11: codes and scale bytes go into the MX-scaled matrix core as stored, see the field).  quant_type is accepted and ignored; the
  * per-row fp32 scale every epilogue multiplies by is 1.0f.  Image: N * K / 2 code bytes in 16-row x 128-k tiles, then the scale
  * plane of N * ceil(K / 512) * 16 bytes (= N * K / 32 when K % 512 == 0), one allocation.  Tensor parallelism (tp_degree > 1)
- * is refused for this dtype; prefill_fp8_activations / prefill_int8_activations are ignored (weight-only everywhere). */
+ * is refused for this dtype; prefill_int8_activations is ignored. */
 /* "quantization_type" (loader.py:892-894) */
 enum { MI_Q_PER_TENSOR_SYMMETRIC = 0, MI_Q_PER_CHANNEL_SYMMETRIC = 1 };
 enum { MI_ROPE_DEFAULT = 0, MI_ROPE_LLAMA3 = 1 };
@@ -88,7 +89,11 @@ typedef struct mi_model_config {
   int32_t use_graphs; /* capture token-generation steps into hipGraphs */
   /* Context-encoding GEMMs (rows > 16) on FP8 weights take per-token dynamically quantized FP8
    * activations and run on the MX-scaled MFMA at twice the bf16 rate; token generation (HBM-bound)
-   * keeps bf16 activations.  0 = weight-only everywhere. */
+   * keeps bf16 activations.  0 = weight-only everywhere.
+   * MI_W_MXFP4 weights (ABI 11): projections over more than 32 rows quantize their input the same way (s = amax / 448, an
+   * all-zero token s = 1, RNE e4m3) and run v_mfma_scale_f32_16x16x128_f8f6f4 with the stored FP4 code tiles as one operand and
+   * the stored e8m0 bytes as its block scales: y = (sum_k q_x * e2m1(code) * 2^E) * s_x * scale, every product exact in fp32.
+   * Up to 32 rows keep the weight-only GEMV. */
   int32_t prefill_fp8_activations;
   /* Tensor parallelism inside ONE process, the reference's process model (a single worker drives
    * every core: platform.py:166-167, neuron_worker.py:106-121): tp_rank = MI_TP_ALL_RANKS makes the
@@ -125,7 +130,7 @@ enum { MI_KV_BF16 = 0, MI_KV_F8E4M3 = 1 };
 enum { MI_TP_TRANSPORT_P2P = 0, MI_TP_TRANSPORT_RCCL = 1 };
 
 const char* mi_last_error(void);
-int mi_version(void);   /* 10 = this header (+ MI_W_MXFP4: 4-bit block-scaled weights through weight_dtype, mi_op_quantize_weight, mi_op_untile_weight, mi_op_qlinear); 9 lacked it (+ prefill_int8_activations, mi_op_qlinear_a8_i8: INT8 x INT8 context-encoding GEMM); 8 lacked them (+ sliding_window, mi_op_paged_attn_decode_sw, mi_op_paged_attn_prefill_sw: Mistral); 7 lacked them (+ qk_norm, mi_op_qk_norm_rope_kv: Qwen3); 6 lacked them (+ mi_op_paged_attn_prefill_f8: context encoding reads the FP8 pool natively); 5 lacked it (+ kv_cache_dtype and the FP8-KV entry points mi_op_kv_write_f8, mi_op_paged_attn_decode_f8, mi_op_kv_dequant_gather); 4 lacked them (+ mi_tp_plan, mi_tp_info); 3 lacked those; 2 lacked tp_device_ids / tp_transport / MI_TP_ALL_RANKS; 1 lacked mi_forward_tokens, mi_op_sample, mi_tp_init_transport */
+int mi_version(void);   /* 11 = this header (prefill_fp8_activations serves MI_W_MXFP4: FP8 activations x FP4 codes on the MX-scaled MFMA; mi_op_qlinear force_path 8 .. 10; no new symbol or field); 10 lacked it (+ MI_W_MXFP4: 4-bit block-scaled weights through weight_dtype, mi_op_quantize_weight, mi_op_untile_weight, mi_op_qlinear); 9 lacked it (+ prefill_int8_activations, mi_op_qlinear_a8_i8: INT8 x INT8 context-encoding GEMM); 8 lacked them (+ sliding_window, mi_op_paged_attn_decode_sw, mi_op_paged_attn_prefill_sw: Mistral); 7 lacked them (+ qk_norm, mi_op_qk_norm_rope_kv: Qwen3); 6 lacked them (+ mi_op_paged_attn_prefill_f8: context encoding reads the FP8 pool natively); 5 lacked it (+ kv_cache_dtype and the FP8-KV entry points mi_op_kv_write_f8, mi_op_paged_attn_decode_f8, mi_op_kv_dequant_gather); 4 lacked them (+ mi_tp_plan, mi_tp_info); 3 lacked those; 2 lacked tp_device_ids / tp_transport / MI_TP_ALL_RANKS; 1 lacked mi_forward_tokens, mi_op_sample, mi_tp_init_transport */
 
 int mi_ctx_create(const mi_model_config* cfg, mi_ctx** out);
 int mi_ctx_destroy(mi_ctx* ctx);
@@ -342,7 +347,10 @@ int mi_op_untile_weight(const void* tiled, int32_t N, int32_t K, int32_t weight_
 /* y[M, N] fp32 = (x[M, K] bf16 . Wq^T) * scale (+ bias).  M <= 16: weight-streaming GEMV;
  * else MFMA GEMM.  force_path: 0 auto, 1 GEMV, 2 GEMM (picked by size), 3 the wide-N LDS-DMA GEMM (1-byte weights),
  * 4 / 5 that GEMM with K split over 2 / 4 slices at 128-token blocks, 6 / 7 at 256-token blocks (K / 64 a multiple of the slices).
- * MI_W_MXFP4: gemv_w4_kernel (M <= 32) / gemm_w4_kernel; force_path 0, 1, 2 only (3 .. 7: MI_EINVAL). */
+ * MI_W_MXFP4: gemv_w4_kernel (M <= 32) / gemm_w4_kernel; force_path 0, 1, 2 (3 .. 7: MI_EINVAL) and, ABI 11, 8 .. 10: x is
+ * quantized per token to e4m3 inside the call (as mi_op_qlinear_a8 does) and multiplied with the FP4 codes by gemm_a8w4_kernel --
+ * 8 with the kernel's own choice of K-split, 9 / 10 with 2 / 4 K-slices of whole scale words (512 k) into an fp32 slab the call
+ * allocates and frees (MI_EINVAL when ceil(K / 512) is smaller than the slice count).  8 .. 10 with any other weight dtype: MI_EINVAL. */
 int mi_op_qlinear(const void* x_bf16, int32_t M, const void* w_tiled, const float* scale,
                   const float* bias, int32_t N, int32_t K, int32_t weight_dtype, float* y,
                   int32_t force_path, void* stream);

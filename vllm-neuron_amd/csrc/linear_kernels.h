@@ -72,9 +72,15 @@ int launch_gemm_wide(const LinearW& w, int T, const uint16_t* x, int ldx, int ep
 // M > 16 with FP8 activations: x8 = K-step-major e4m3 image [K / 128][ldx >= T rows][128 B] as
 // launch_rowquant_fp8 writes it (per-token scale in EpiArgs::row_scale), FP8 weights,
 // MX-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4, unit block scales) at twice the bf16 rate.
+// MXFP4 weights: launch_gemm_a8w4.  supported: FP8 or MXFP4 weights, K % 128 == 0, N % 16 == 0.
 int launch_gemm_a8(const LinearW& w, int T, const uint8_t* x8, int ldx, int epi, const EpiArgs& e,
                    hipStream_t s, float* splitk_ws = nullptr, size_t splitk_ws_bytes = 0, SlabSum* defer = nullptr);
 bool gemm_a8_supported(const LinearW& w);
+// The same activations on MXFP4 weights: the code tiles are the instruction's FP4 A operand and the e8m0 scale words its
+// block scales, both as stored.  force_ks (mi_op_qlinear force_path 9 / 10): that many K-slices of whole scale words
+// (4 k-tiles) instead of gemm_pick_splitk's choice; <= ceil(K / 512).
+int launch_gemm_a8w4(const LinearW& w, int T, const uint8_t* x8, int ldx, int epi, const EpiArgs& e, hipStream_t s,
+                     float* splitk_ws = nullptr, size_t splitk_ws_bytes = 0, SlabSum* defer = nullptr, int force_ks = 0);
 // bf16 rows -> K-step-major e4m3 image [K / 128][T][128 B] + per-row scale (amax / 448; all-zero row -> 1)
 int launch_rowquant_fp8(const uint16_t* x, int T, int K, int ldx, uint8_t* x8, float* row_scale, hipStream_t s);
 // M > 16 with INT8 activations on INT8 weights: x8 = the same K-step-major image holding int8 codes as

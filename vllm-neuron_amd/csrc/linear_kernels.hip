@@ -21,12 +21,15 @@
 // Prefill (M > 16): gemm_kernel — 128 x 128 tile, x through swizzled LDS, W straight
 //   from global in fragment order.
 //
-// MXFP4 (4-bit codes + one power-of-two scale per 32 k, mi_common.h): 16 x 128 tiles; gemv_w4_kernel / gemm_w4_kernel.
+// MXFP4 (4-bit codes + one power-of-two scale per 32 k, mi_common.h): 16 x 128 tiles; gemv_w4_kernel / gemm_w4_kernel, and
+//   gemm_a8w4_kernel: FP8 activations against the codes and scales as stored, on the block-scaled MFMA.
 //
 // Both share one epilogue on D[n = 4g + r][m = c] (lane = 16 g + c): dequant scale, bias,
 // then fp32 store | RoPE + q/KV-pool scatter | SwiGLU.
 
 #include "linear_kernels.h"
+
+#include <type_traits>
 
 namespace mi {
 
@@ -2673,14 +2676,15 @@ int launch_splitk_flush(const SlabSum& sl, const float* resid_in, float* out, in
 }
 
 bool gemm_a8_supported(const LinearW& w) {
-  return w.wd == MI_W_F8E4M3 && w.K % kA8BK == 0 && w.N % 16 == 0;
+  return (w.wd == MI_W_F8E4M3 || w.wd == MI_W_MXFP4) && w.K % kA8BK == 0 && w.N % 16 == 0;
 }
 
 int launch_gemm_a8(const LinearW& w, int T, const uint8_t* x8, int ldx, int epi, const EpiArgs& e, hipStream_t s,
                    float* splitk_ws, size_t splitk_ws_bytes, SlabSum* defer) {
   if (defer) *defer = SlabSum();
   MI_CHECK(T >= 1, "gemm_a8: T must be >= 1");
-  MI_CHECK(gemm_a8_supported(w), "gemm_a8: needs fp8 weights, K % 128 == 0, N % 16 == 0");
+  MI_CHECK(gemm_a8_supported(w), "gemm_a8: needs fp8 or MXFP4 weights, K % 128 == 0, N % 16 == 0");
+  if (w.wd == MI_W_MXFP4) return launch_gemm_a8w4(w, T, x8, ldx, epi, e, s, splitk_ws, splitk_ws_bytes, defer);   // FP4 A operand, real block scales
   MI_CHECK(ldx >= T && e.row_scale != nullptr, "gemm_a8: x8 is the K-step-major image of >= T rows, with its row scales");
   const int NT = w.N / 16, KT = w.K / 64, nks = w.K / kA8BK;
   {   // The wide tile (MI355X_A8_WIDE: 0 never, 1 always, unset: by plan) where its one-work-group-per-CU grid fills one or two
@@ -2937,6 +2941,227 @@ int launch_gemm_a8i(const LinearW& w, int T, const uint8_t* x8, int ldx, int epi
   else if (epi == EPI_RESID) MI_A8I(EPI_RESID);
   else MI_A8I(EPI_F32);
 #undef MI_A8I
+  MI_HIP(hipGetLastError());
+  return MI_OK;
+}
+
+// =====================================================================================
+// GEMM with FP8 activations on MXFP4 weights (context encoding, the block-scaled contraction)
+// =====================================================================================
+// y[m, n] = (sum_k q_x[m, k] * e2m1(code[n, k]) * 2^E[n, k / 32]) * s_x[m] * scale[n]: every product exact in fp32.
+// v_mfma_scale_f32_16x16x128_f8f6f4 with cbsz = 4 takes an FP4 A operand: lane (g = lane >> 4, r = lane & 15) supplies
+// 16 bytes = the 32 codes of row r, k = 32 g .. 32 g + 31 in k order (even k in the low nibble), and ONE e8m0 byte for
+// them, picked out of a scale register by op_sel.  That is the lane's 16 bytes of the stored 16 x 128 tile and byte
+// kt & 3 of its stored scale word (mi_common.h): codes and scales go from global memory into the matrix core as stored,
+// a 16-byte load per (n-tile, k-tile) and a 4-byte load per (n-tile, 4 k-tiles) per lane, and no ALU instruction touches
+// them.  The B operand is e4m3 with unit block scales, and the contraction index is the instruction's own: the 32 codes
+// of A lane group g are its k = 32 g .. 32 g + 31, while an 8-bit lane of group g holds k = 16 g .. 16 g + 15 in its
+// first four registers and k = 64 + 16 g .. 64 + 16 g + 15 in the other four (read off the device with one-hot
+// activations: the first 16 bytes of a B lane of group 0 met weight k 0 .. 15, its second 16 bytes weight k 64 .. 79).
+// Lane (g, c) therefore supplies the 16-byte chunks g and 4 + g of token row c of the K-step, as in gemm_a8_kernel --
+// there the order was free because both operands were permuted together, here the stored FP4 image fixes it.  The
+// token's fp32 scale goes through EpiArgs::row_scale.
+//
+// Work split: gemm_a8i_kernel's.  4 waves, 128 (n) x 128 (m) x one 128-k tile per K-step; wave w owns n-tiles 2w, 2w + 1
+// against all 8 m-tiles: 16 MFMAs a K-step on two 4-register weight fragments and 16 LDS reads, a B fragment feeding both
+// n-tiles.  XCD-aware tile order as in gemm_a8_kernel.
+// Weight stream: op_sel is an immediate, so the K loop is unrolled over the 4 k-tiles of a scale word (a batch: 4 x 16 B
+// per lane and n-tile, 1 KiB per wave, contiguous in the image).  The fragments sit in a ring of four slots per n-tile:
+// as soon as the MFMAs of k-tile kt have read slot kt & 3, the slot is re-requested with k-tile kt + 4, so three to four
+// K-steps of MFMAs (48 .. 64) cover every weight load, on 32 registers -- what gemm_a8_kernel spends on ONE K-step of FP8
+// weights and its copy.  The next batch's scale words are requested at the start of the current batch.  K-slices (SPLIT)
+// start at multiples of 4 k-tiles, so a batch never straddles a scale word; only the last batch of a slice can be short
+// (KT % 4 k-tiles): its missing k-tiles are neither requested nor multiplied (their scale bytes are 127, but the code
+// tiles do not exist).
+// LDS: two stages of 128 token rows x 128 B (32 KiB), filled like gemm_a8i_kernel's: K-step kt + 1 is fetched into
+// registers before the MFMAs of K-step kt and stored to the other stage after them, one barrier per K-step.  The 16-byte
+// chunk ch of row r lies at slot ch ^ (r & 7) of the row's 8 (xs_swz<MI_W_BF16>): the fragment reads are (row c, chunks g
+// and 4 + g), gemm_kernel's bf16-weight read pattern, which that key makes conflict-free over the ds_read_b128 lane
+// groups (see xs_swz; enumerated again for this kernel, as is the 160-byte pitch of kA8Pitch, which costs 8 KiB more).
+// The key of row 16 mt + c does not depend on mt, and a staging store (8 lanes a row, two rows per 16 lanes) writes a
+// permutation of each row's 8 slots: conflict-free too.
+// Registers per lane: 64 accumulators, 32 weight ring, 4 scale words, 16 staged activations, 8 B operand: three work-groups
+// a CU (96 KiB of LDS), as the siblings.
+constexpr int kA8w4Stage = kA8BM * 8;   // uint4 slots of one LDS stage (16 KiB)
+
+template <int EPI, bool SPLIT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void gemm_a8w4_kernel(
+    const uint4* __restrict__ W, const uint32_t* __restrict__ S, int NT, int KT, int T, const uint8_t* __restrict__ x8, int ldx,
+    EpiArgs e, float* __restrict__ slab) {
+  __shared__ __attribute__((aligned(16))) uint4 xs[2 * kA8w4Stage];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // the weight and scale addresses below are scalar + lane offset
+  const int g = lane >> 4, c = lane & 15;
+  constexpr int NTW = 2, BNT = 4 * NTW;   // n-tiles per wave / per work-group
+  const int mtiles = ceil_div(T, kA8BM), ntiles = ceil_div(NT, BNT);
+  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
+  const int mblk = seq % mtiles, nblk = (seq / mtiles) * 8 + xcd;
+  if (nblk >= ntiles) return;
+  const int m0 = mblk * kA8BM, nt0 = nblk * BNT + wave * NTW;
+  const int KQ = ceil_div(KT, kW4U);
+  const int kq_per = SPLIT ? ceil_div(KQ, (int)gridDim.z) : KQ;     // a slice is whole scale words
+  const int kt_beg = SPLIT ? (int)blockIdx.z * kq_per * kW4U : 0;
+  const int kt_end = min(kt_beg + kq_per * kW4U, KT);               // exclusive (an empty slice writes zeros)
+  const int kt_last = kt_end - 1;
+  constexpr int kUnit = 0x7f7f7f7f;   // E8M0 block scales of the activations: 2^0
+
+  f32x4_t acc[NTW][8];
+#pragma unroll
+  for (int i = 0; i < NTW; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  // x staging: 128 rows x 128 B per K-step = 1024 chunks of 16 B, 4 per thread (rows tid / 8 + 32 i, chunk tid % 8: the key
+  // is the same for all four), 16 KiB contiguous in the K-step-major image.  Rows past T: a copy of the last row, never
+  // stored; n-tiles past NT likewise the last tile.
+  const int srow = tid >> 3, sch = tid & 7;
+  const int xdst = srow * 8 + (sch ^ xs_swz<MI_W_BF16>(srow));
+  uint32_t xoff[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) xoff[i] = (uint32_t)min(m0 + srow + 32 * i, T - 1) * kA8BK + sch * 16;
+  const uint4* wsrc[NTW];
+  const uint32_t* ssrc[NTW];
+#pragma unroll
+  for (int i = 0; i < NTW; ++i) {
+    const int nt = min(nt0 + i, NT - 1);
+    wsrc[i] = W + (size_t)nt * KT * 64;
+    ssrc[i] = S + (size_t)nt * KQ * 64;
+  }
+  u32x4_t xr[4], wr[NTW][kW4U];
+  uint32_t sw[NTW], swn[NTW];
+  // Every global address of the loop is a scalar base + a 32-bit lane offset.  The offset is passed through an empty asm so
+  // that its zero-extension stays next to the load and the load takes the (scalar base, 32-bit offset) form: hoisted out of
+  // the loop it becomes a 64-bit register pair per address, and the kernel no longer fits three waves a SIMD.
+  auto vofs = [](uint32_t o) { asm volatile("" : "+v"(o)); return o; };
+  const uint32_t lane16 = lane * 16, lane4 = lane * 4;
+  // Inside a slice nothing is predicated: a request past the slice's end re-requests its last k-tile (K-step, scale word),
+  // which exists; what it brings is never multiplied.
+  auto load_x = [&](int kt) {
+    const uint8_t* base = x8 + (size_t)min(kt, kt_last) * ldx * kA8BK;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xr[i] = *reinterpret_cast<const u32x4_t*>(base + vofs(xoff[i]));
+  };
+  auto store_x = [&](int stage) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4_t*>(&xs[stage * kA8w4Stage + xdst + i * 32 * 8]) = xr[i];
+  };
+  auto load_w = [&](int u, int kt) {
+#pragma unroll
+    for (int i = 0; i < NTW; ++i)
+      wr[i][u] = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const unsigned char*>(wsrc[i] + (size_t)min(kt, kt_last) * 64) + vofs(lane16));
+  };
+  auto load_s = [&](uint32_t (&dst)[NTW], int kq) {
+#pragma unroll
+    for (int i = 0; i < NTW; ++i)
+      dst[i] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const unsigned char*>(ssrc[i] + (size_t)min(kq, kt_last >> 2) * 64) + vofs(lane4));
+  };
+  // the lane's two 16-byte pieces of a B fragment: row 16 mt + c, chunks g and 4 + g
+  const int key = xs_swz<MI_W_BF16>(c);
+  const int xb0 = c * 8 + (g ^ key), xb1 = c * 8 + ((4 + g) ^ key);
+
+  // K-step kt = kb + u of the batch at kb (kb % 4 == 0): op_sel u (an immediate: u arrives as a type), LDS stage u & 1
+  auto step = [&](int kb, auto uc, auto tail) {
+    constexpr int u = decltype(uc)::value;
+    const int kt = kb + u;
+    load_x(kt + 1);
+    __builtin_amdgcn_sched_barrier(0);   // the requests stay in front of the MFMAs that cover them
+    const uint4* xst = &xs[(u & 1) * kA8w4Stage];
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) {
+      const u32x4_t b0 = *reinterpret_cast<const u32x4_t*>(&xst[mt * 16 * 8 + xb0]);
+      const u32x4_t b1 = *reinterpret_cast<const u32x4_t*>(&xst[mt * 16 * 8 + xb1]);
+      const i32x8_t b = {(int)b0[0], (int)b0[1], (int)b0[2], (int)b0[3], (int)b1[0], (int)b1[1], (int)b1[2], (int)b1[3]};
+#pragma unroll
+      for (int i = 0; i < NTW; ++i) {
+        // FP4 A: the instruction reads the first four registers of the operand; the rest stay undefined so that none is spent
+        const i32x4_t w4 = __builtin_bit_cast(i32x4_t, wr[i][u]);
+        const i32x8_t a = __builtin_shufflevector(w4, w4, 0, 1, 2, 3, -1, -1, -1, -1);
+        acc[i][mt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc[i][mt], 4, 0, u, (int)sw[i], 0, kUnit);
+      }
+    }
+    if constexpr (!decltype(tail)::value) load_w(u, kt + kW4U);   // slot u is read: the next batch's k-tile
+    store_x((u + 1) & 1);   // the other stage: read last in K-step kt - 1, before the barrier every wave has passed
+    __syncthreads();
+  };
+  using std::integral_constant;
+  using std::false_type;
+  using std::true_type;
+
+  if (kt_beg < kt_end) {
+    load_x(kt_beg);
+    load_s(sw, kt_beg >> 2);
+#pragma unroll
+    for (int u = 0; u < kW4U; ++u) load_w(u, kt_beg + u);
+    store_x(0);
+  }
+  __syncthreads();
+  int kb = kt_beg;
+  for (; kb + kW4U <= kt_end; kb += kW4U) {   // whole batches
+    load_s(swn, (kb >> 2) + 1);
+    step(kb, integral_constant<int, 0>{}, false_type{});
+    step(kb, integral_constant<int, 1>{}, false_type{});
+    step(kb, integral_constant<int, 2>{}, false_type{});
+    step(kb, integral_constant<int, 3>{}, false_type{});
+#pragma unroll
+    for (int i = 0; i < NTW; ++i) sw[i] = swn[i];
+  }
+  // the short last batch of a slice (KT % 4 k-tiles): the ring holds its tiles, sw its scale word
+  if (kb < kt_end) step(kb, integral_constant<int, 0>{}, true_type{});
+  if (kb + 1 < kt_end) step(kb, integral_constant<int, 1>{}, true_type{});
+  if (kb + 2 < kt_end) step(kb, integral_constant<int, 2>{}, true_type{});
+
+#pragma unroll
+  for (int i = 0; i < NTW; ++i) {
+    if (nt0 + i >= NT) continue;
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) {
+      const int m = m0 + mt * 16 + c;
+      if (m >= T) continue;
+      const int n0 = (nt0 + i) * 16 + g * 4;
+      if constexpr (SPLIT) {
+        *reinterpret_cast<float4*>(slab + ((size_t)blockIdx.z * T + m) * (NT * 16) + n0) =
+            make_float4(acc[i][mt][0], acc[i][mt][1], acc[i][mt][2], acc[i][mt][3]);
+      } else {
+        epilogue<EPI>(e, m, n0, acc[i][mt]);
+      }
+    }
+  }
+}
+
+int launch_gemm_a8w4(const LinearW& w, int T, const uint8_t* x8, int ldx, int epi, const EpiArgs& e, hipStream_t s,
+                     float* splitk_ws, size_t splitk_ws_bytes, SlabSum* defer, int force_ks) {
+  if (defer) *defer = SlabSum();
+  MI_CHECK(T >= 1, "gemm_a8w4: T must be >= 1");
+  MI_CHECK(w.wd == MI_W_MXFP4 && gemm_a8_supported(w), "gemm_a8w4: needs MXFP4 weights, K % 128 == 0, N % 16 == 0");
+  MI_CHECK(ldx >= T && e.row_scale != nullptr, "gemm_a8w4: x8 is the K-step-major image of >= T rows, with its row scales");
+  const int NT = w.N / 16, KT = w.K / 128, KQ = ceil_div(KT, kW4U);
+  const int mtiles = ceil_div(T, kA8BM), ntiles = ceil_div(w.N, 128);
+  // slices are whole scale words (4 k-tiles), so at most KQ of them
+  int KS = gemm_pick_splitk(mtiles * ntiles, KQ, T, w.N, splitk_ws ? splitk_ws_bytes : 0);
+  if (force_ks) {
+    MI_CHECK(force_ks >= 1 && force_ks <= KQ && (force_ks == 1 || (splitk_ws && (size_t)force_ks * T * w.N * 4 <= splitk_ws_bytes)),
+             "gemm_a8w4: forced K-split must not exceed ceil(K / 512) and must fit the workspace");
+    KS = force_ks;
+  }
+  const uint4* W = reinterpret_cast<const uint4*>(w.w);
+  const uint32_t* S = reinterpret_cast<const uint32_t*>(reinterpret_cast<const unsigned char*>(w.w) + (size_t)w.N * w.K / 2);
+  dim3 grid(8 * mtiles * ceil_div(ntiles, 8), 1, KS);   // see gemm_a8_kernel: XCD-aware tile order
+#define MI_A8W4(EPI_) \
+  do { \
+    if (KS == 1) { \
+      hipLaunchKernelGGL((gemm_a8w4_kernel<EPI_, false>), grid, dim3(256), 0, s, W, S, NT, KT, T, x8, ldx, e, nullptr); \
+    } else { \
+      hipLaunchKernelGGL((gemm_a8w4_kernel<EPI_, true>), grid, dim3(256), 0, s, W, S, NT, KT, T, x8, ldx, e, splitk_ws); \
+      if (defer && EPI_ == EPI_RESID) { *defer = SlabSum{splitk_ws, KS, T, w.N, e.scale, e.bias, e.row_scale}; } \
+      else hipLaunchKernelGGL((splitk_reduce_kernel<EPI_>), dim3(ceil_div(T * (w.N / 4), 256)), dim3(256), 0, s, splitk_ws, KS, T, w.N, e); \
+    } \
+  } while (0)
+  if (epi == EPI_QKV) MI_A8W4(EPI_QKV);
+  else if (epi == EPI_QKV_F8) MI_A8W4(EPI_QKV_F8);
+  else if (epi == EPI_SWIGLU) MI_A8W4(EPI_SWIGLU);
+  else if (epi == EPI_RESID) MI_A8W4(EPI_RESID);
+  else MI_A8W4(EPI_F32);
+#undef MI_A8W4
   MI_HIP(hipGetLastError());
   return MI_OK;
 }

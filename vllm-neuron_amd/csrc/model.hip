@@ -655,7 +655,7 @@ int capture_or_launch_decode(mi_ctx* c, int B, int MB) {
 extern "C" {
 
 const char* mi_last_error(void) { return mi::g_err.c_str(); }
-int mi_version(void) { return 10; }   // 10: + MI_W_MXFP4 (4-bit block-scaled weights: gemv_w4_kernel, gemm_w4_kernel); 9: + prefill_int8_activations, mi_op_qlinear_a8_i8 (INT8 x INT8 context-encoding GEMM); 8: + sliding_window, mi_op_paged_attn_decode_sw / mi_op_paged_attn_prefill_sw (Mistral); 7: + qk_norm, mi_op_qk_norm_rope_kv (Qwen3); 6: + mi_op_paged_attn_prefill_f8; 5: + kv_cache_dtype, mi_op_kv_write_f8 / mi_op_paged_attn_decode_f8 / mi_op_kv_dequant_gather; 4: + mi_tp_plan, mi_tp_info; 3: + in-process tensor parallelism (tp_rank = MI_TP_ALL_RANKS, tp_device_ids, tp_transport)
+int mi_version(void) { return 11; }   // 11: prefill_fp8_activations serves MI_W_MXFP4 (gemm_a8w4_kernel: FP8 activations x FP4 codes on the block-scaled MFMA), mi_op_qlinear force_path 8 .. 10; 10: + MI_W_MXFP4 (4-bit block-scaled weights: gemv_w4_kernel, gemm_w4_kernel); 9: + prefill_int8_activations, mi_op_qlinear_a8_i8 (INT8 x INT8 context-encoding GEMM); 8: + sliding_window, mi_op_paged_attn_decode_sw / mi_op_paged_attn_prefill_sw (Mistral); 7: + qk_norm, mi_op_qk_norm_rope_kv (Qwen3); 6: + mi_op_paged_attn_prefill_f8; 5: + kv_cache_dtype, mi_op_kv_write_f8 / mi_op_paged_attn_decode_f8 / mi_op_kv_dequant_gather; 4: + mi_tp_plan, mi_tp_info; 3: + in-process tensor parallelism (tp_rank = MI_TP_ALL_RANKS, tp_device_ids, tp_transport)
 
 int mi_tp_plan(const mi_model_config* cfg, int32_t rank, mi_tp_plan_t* out) {
   MI_CHECK(cfg && out, "null argument");
@@ -1890,7 +1890,36 @@ int mi_op_qlinear(const void* x, int32_t M, const void* w_tiled, const float* sc
   LinearW W{w_tiled, N, K, wd};
   if (wd == MI_W_MXFP4) {
     MI_CHECK(N % 16 == 0 && K % 128 == 0, "qlinear: MXFP4 weights need N % 16 == 0 and K % 128 == 0");
-    MI_CHECK(force_path >= 0 && force_path <= 2, "qlinear: MXFP4 weights take force_path 0, 1 or 2 (no wide-N GEMM)");
+    MI_CHECK((force_path >= 0 && force_path <= 2) || (force_path >= 8 && force_path <= 10),
+             "qlinear: MXFP4 weights take force_path 0, 1, 2 or 8 .. 10 (no wide-N GEMM)");
+  } else {
+    MI_CHECK(force_path < 8 || force_path > 10, "qlinear: force_path 8 .. 10 (the FP8-activation GEMM on FP4 codes) need MXFP4 weights");
+  }
+  if (force_path >= 8 && force_path <= 10) {   // gemm_a8w4_kernel: 8 = its own K-split, 9 / 10 = 2 / 4 slices into a slab of the call's
+    const int ks = force_path == 8 ? 0 : (force_path == 9 ? 2 : 4);
+    MI_CHECK(M >= 1 && ks <= (K + 511) / 512, "qlinear: force_path 9 / 10 need ceil(K / 512) >= 2 / 4 (slices are whole scale words)");
+    const size_t slab_bytes = (size_t)ks * M * N * 4;
+    uint8_t* x8 = nullptr;
+    float *xs = nullptr, *slab = nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = MI_OK;
+    if (hipMalloc(reinterpret_cast<void**>(&x8), (size_t)M * K) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&xs), (size_t)M * 4) != hipSuccess ||
+        (slab_bytes && hipMalloc(reinterpret_cast<void**>(&slab), slab_bytes) != hipSuccess)) {
+      set_error("qlinear: out of device memory");
+      rc = MI_EHIP;
+    }
+    if (rc == MI_OK) rc = launch_rowquant_fp8(reinterpret_cast<const uint16_t*>(x), M, K, K, x8, xs, s);
+    if (rc == MI_OK) {
+      EpiArgs e{};
+      e.scale = scale; e.bias = bias; e.out_f32 = y; e.ld_out = N; e.row_scale = xs;
+      rc = launch_gemm_a8w4(W, M, x8, M, EPI_F32, e, s, slab, slab_bytes, nullptr, ks);
+    }
+    hipStreamSynchronize(s);
+    hipFree(x8);
+    hipFree(xs);
+    hipFree(slab);
+    return rc;
   }
   EpiArgs e{};
   e.scale = scale; e.bias = bias; e.out_f32 = y; e.ld_out = N;
